@@ -22,9 +22,15 @@ collective the path needs.
 
 `value` = field values decoded+filtered per second, whole-job across all
 ranks.  A "value" is one point of the measured f64 field column (1e7*N
-series-points per step... see config).  Roofline + cpu_baseline objects
-per the driver contract; the roofline covers the dominant kernel
-(k_gor_lds_filtered, the fused Gorilla page decoder).
+series-points per step... see config).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps steps, print one JSON line (`roofline` and `cpu_baseline`
+null).  `--full` adds the roofline calibration pass (dominant kernel
+k_gor_lds_filtered, the fused Gorilla page decoder), the cpu_baseline leg
+and, in groupby mode, the isolated group-by loop.  `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy (float64; row
+outputs as a fixed seeded sample) so two builds can be compared.
 """
 import argparse
 import json
@@ -46,7 +52,60 @@ def _host_threads():
     """OMP threads per rank: divide the host cores among co-located ranks
     (the round-end 8-GPU run launches 8 ranks on one node)."""
     lw = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
-    return max(1, (os.cpu_count() or 8) // max(1, lw))
+    # the cores this process may actually use (affinity mask, capped by
+    # OMP_NUM_THREADS), not the machine's: a team sized by os.cpu_count()
+    # inside a smaller CPU allotment only slows the setup encoder down
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 8
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n // max(1, lw))
+
+
+DUMP_SAMPLE_ROWS = 1 << 18  # rows sampled per dumped row-output array
+
+
+def _sample_rows(n, seed=231):
+    """Row indices to dump from an n-row output: all of them when small,
+    else a fixed seeded sample (sorted), identical from run to run."""
+    if n <= DUMP_SAMPLE_ROWS:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    return np.sort(rng.integers(0, n, DUMP_SAMPLE_ROWS, dtype=np.int64))
+
+
+def _take(d_arr, idx, base=0):
+    """Gather d_arr[base + idx] from a device tensor to a host array."""
+    import torch
+    if idx.size == 0:
+        return np.zeros(0)
+    return d_arr[torch.from_numpy(idx + base).to(d_arr.device)].cpu().numpy()
+
+
+def _max_for_dump(d_max, d_count):
+    """Per-bucket max as dumped: a bucket no row fell into holds the
+    engine's -inf identity, which a caller never reads (count == 0 there);
+    it is written as 0.0 so that every dumped value is finite.  Buckets
+    with rows are written as computed, whatever they hold."""
+    mx = d_max.cpu().numpy().copy()
+    mx[d_count.cpu().numpy() == 0] = 0.0
+    return mx
+
+
+def dump_outputs(dirpath, arrays, rank=0):
+    """--dump-outputs: write {name: array} as DIR/<name>.npy in float64
+    (float32 stays float32).  int64 timestamps are passed in relative to
+    T0 so that they stay exact in float64."""
+    os.makedirs(dirpath, exist_ok=True)
+    prefix = f"rank{rank}_" if rank else ""
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirpath, prefix + name + ".npy"), a)
 
 
 def build_workload(nseries, npts, page_rows, unique, sub_batches, nfields=1, seed=231):
@@ -266,22 +325,30 @@ def bench_compact(args):
                              d_enc_ts, cap)
         lens = eng.encode_pages_dev(2, d_oval, np.array(row_off),
                                     np.array(rows_arr), d_enc_v, cap)
-        return out_rows, int(lens.sum())
+        return out_rows, int(lens.sum()), offs
 
     for _ in range(args.warmup):
-        out_rows, enc_bytes = step()
+        out_rows, enc_bytes, offs = step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        out_rows, enc_bytes = step()
+        out_rows, enc_bytes, offs = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     value = total * args.steps / dt
+    if args.dump_outputs:
+        idx = _sample_rows(int(out_rows))
+        dump_outputs(args.dump_outputs, {
+            "sample_rows": idx,
+            "merged_ts_minus_t0_ns": _take(d_ots, idx) - T0,
+            "merged_val": _take(d_oval, idx),
+            "series_offsets": offs,
+        })
 
     # CPU baseline: oracle C k-way merge (OpenMP over series) + host
     # re-encode on a bounded sample
     cpu_baseline = None
-    if not args.skip_cpu_baseline:
+    if args.full and not args.skip_cpu_baseline:
         import ctypes
         from oracle import pyoracle as orc
 
@@ -439,9 +506,24 @@ def bench_strings(args):
     dt = time.perf_counter() - t0
     assert got == total_payload
     value = total_rows * args.steps / dt
+    if args.dump_outputs:
+        # first resident set: sampled Arrow offsets + a fixed 64-byte
+        # window of string bytes at each of the first 65536 sampled rows
+        gset, d_off, d_bytes = sets[0]
+        idx = _sample_rows(gset.rows)
+        starts = _take(d_off, idx)
+        win = (starts[:1 << 16, None]
+               + np.arange(64, dtype=np.int64)).reshape(-1)
+        win = np.minimum(win, d_bytes.numel() - 1)
+        dump_outputs(args.dump_outputs, {
+            "sample_rows": idx,
+            "str_offsets": starts,
+            "str_offsets_end": _take(d_off, idx, base=1),
+            "str_bytes_window": _take(d_bytes, win).astype(np.float32),
+        })
 
     cpu_baseline = None
-    if not args.skip_cpu_baseline:
+    if args.full and not args.skip_cpu_baseline:
         import ctypes
         from oracle import pyoracle as orc
         o = orc.Oracle().lib
@@ -643,8 +725,18 @@ def bench_general(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0_
     value = rows * args.steps / dt
+    if args.dump_outputs:
+        idx = _sample_rows(int(r.out_rows))
+        dump_outputs(args.dump_outputs, {
+            "sample_rows": idx,
+            "out_ts_minus_t0_ns": _take(d_ots, idx) - T0,
+            "out_val": _take(d_oval, idx),
+            "agg_max": _max_for_dump(agg["d_max"], agg["d_count"]),
+            "agg_sum": agg["d_sum"].cpu().numpy(),
+            "agg_count": agg["d_count"].cpu().numpy(),
+        })
     cpu_baseline = None
-    if not args.skip_cpu_baseline:
+    if args.full and not args.skip_cpu_baseline:
         cpu_baseline = cpu_baseline_general(16, npts, page_rows, lo, hi,
                                             tstones, pred[1])
     line = {
@@ -741,13 +833,22 @@ def bench_groupby(args):
         ngids, _ = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0_
-    # isolate the group-by increment
-    torch.cuda.synchronize()
-    t1_ = time.perf_counter()
-    for _ in range(args.steps):
-        gs.groupby_tag(eng, gset, nb, g_max, g_sum, g_cnt, cap)
-    torch.cuda.synchronize()
-    gb_ms = (time.perf_counter() - t1_) / args.steps * 1000
+    if args.dump_outputs:
+        n = int(ngids) * nb
+        dump_outputs(args.dump_outputs, {
+            "group_max": _max_for_dump(g_max[:n], g_cnt[:n]),
+            "group_sum": g_sum[:n].cpu().numpy(),
+            "group_count": g_cnt[:n].cpu().numpy(),
+        })
+    # isolate the group-by increment (a timed loop of its own: --full)
+    gb_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        t1_ = time.perf_counter()
+        for _ in range(args.steps):
+            gs.groupby_tag(eng, gset, nb, g_max, g_sum, g_cnt, cap)
+        torch.cuda.synchronize()
+        gb_ms = (time.perf_counter() - t1_) / args.steps * 1000
     value = rows * args.steps / dt
     line = {
         "metric": "decoded+filtered values/sec & HBM GB/s, TSBS devops scan, 1/2/4/8 GPU",
@@ -787,6 +888,15 @@ def main():
     ap.add_argument("--fields", type=int, default=1,
                     help="f64 field pages per group (8 = TSBS cpu-max-all-8, config #3)")
     ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: "
+                         "the cpu_baseline leg, the roofline calibration "
+                         "pass (scan) and the isolated group-by loop "
+                         "(groupby); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed as DIR/<name>.npy (float64; row "
+                         "outputs as a fixed seeded sample)")
     args = ap.parse_args()
 
     if args.mode == "compact":
@@ -892,6 +1002,8 @@ def main():
               torch.zeros(1, dtype=torch.float64, device=device))
              for _ in range(2)]
 
+    set_out_rows = [0] * len(sets)  # per-set selected rows of the last step
+
     def step():
         out_rows = 0
         phase_ms = np.zeros(5)
@@ -905,6 +1017,7 @@ def main():
                                  douts[i % 2][1], aggs[i % 2])
         for i, st_ in enumerate(sets):
             r = eng_of[i].scan_wait(st_)
+            set_out_rows[i] = r.out_rows
             out_rows += r.out_rows * nf
             phase_ms += [r.ms_decode_ts, r.ms_decode_val, r.ms_filter,
                          r.ms_compact, r.ms_agg]
@@ -942,52 +1055,73 @@ def main():
         dist.all_reduce(t_t, op=dist.ReduceOp.MAX)
         dt = float(t_t.item())
 
-    # clean (unoverlapped) per-kernel timings for the roofline: one extra
-    # scan on a single stream, untimed region (stream-distance HIP events
-    # are inflated by cross-stream overlap during the timed steps)
-    engines[0].scan_async(sets[0], douts[0][0], douts[0][1],
-                          time_range=(lo, hi), agg=aggs[0], field_col=0)
-    r_cal = engines[0].scan_wait(sets[0])
-
     values_per_step = nseries * npts * args.fields  # field values decoded+filtered per rank
     total_values = values_per_step * world * args.steps
     value = total_values / dt
     ms_per_step = dt / args.steps * 1000
 
-    # roofline: dominant kernel = k_gor_lds_filtered (fused Gorilla decode),
-    # 1 launch per sub-batch. algorithmic bytes per launch = compressed f64
-    # bytes read + 8 B per SELECTED row written (the fused kernel skips the
-    # stores of filtered-out rows; SURVEY.md §8d: count bytes actually
-    # moved).  The unfused number (8 B x all rows) is stated in DESIGN.md.
-    raw_f64_bytes = raw_f64_bytes_sb0 - \
-        (16 + (page_rows + 7) // 8) * (sb_rows // page_rows)
-    sel_rows_sb = int(out_rows) // args.sub_batches
-    alg_bytes_launch = raw_f64_bytes + 8 * sel_rows_sb
-    ms_gorilla_launch = r_cal.ms_decode_val
-    achieved = alg_bytes_launch / (ms_gorilla_launch / 1000) if ms_gorilla_launch > 0 else 0
-    peak = 8.0e12
-    traffic = None
-    pmc_path = os.path.join(REPO, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc_path):
-        try:
-            pmc = json.load(open(pmc_path))
-            shape = pmc.get("launch_shape", {})
-            # attach only when the PMC collection ran the same launch
-            # shape (a stale half-size traffic number
-            # was attached to a full-size run)
-            if (pmc.get("kernel") == "k_gor_chunks_filtered"
-                    and shape.get("rows_per_launch") == sb_rows
-                    and shape.get("page_rows") == page_rows
-                    and shape.get("sub_batches") == args.sub_batches
-                    and shape.get("series") == nseries):
-                traffic = pmc.get("bytes_per_launch")
-        except Exception:
-            pass
-    roofline = {"bound": "hbm", "achieved": achieved, "peak": peak,
-                "unit": "B/s", "frac": achieved / peak, "traffic": traffic}
+    if args.dump_outputs:
+        # what a caller of step() holds after the last timed step: the
+        # combined per-bucket aggregates and, per output buffer, the
+        # compacted rows of the last set scanned into it (sampled)
+        arrays = {"agg_sum": d_sum.cpu().numpy(),
+                  "agg_count": d_cnt.cpu().numpy(),
+                  "agg_max": _max_for_dump(d_max, d_cnt)}
+        for b_ in range(min(2, len(sets))):
+            i = max(j for j in range(len(sets)) if j % 2 == b_)
+            idx = _sample_rows(int(set_out_rows[i]), seed=231 + b_)
+            arrays[f"buf{b_}_sample_rows"] = idx
+            arrays[f"buf{b_}_out_ts_minus_t0_ns"] = \
+                _take(douts[b_][0], idx) - T0
+            for f in range(nf):
+                arrays[f"buf{b_}_out_val_f{f}"] = \
+                    _take(douts[b_][1], idx, base=f * sb_rows)
+        dump_outputs(args.dump_outputs, arrays, rank)
+
+    roofline = None
+    r_cal = None
+    if args.full:
+        # clean (unoverlapped) per-kernel timings for the roofline: one extra
+        # scan on a single stream, untimed region (stream-distance HIP events
+        # are inflated by cross-stream overlap during the timed steps)
+        engines[0].scan_async(sets[0], douts[0][0], douts[0][1],
+                              time_range=(lo, hi), agg=aggs[0], field_col=0)
+        r_cal = engines[0].scan_wait(sets[0])
+
+        # roofline: dominant kernel = k_gor_lds_filtered (fused Gorilla decode),
+        # 1 launch per sub-batch. algorithmic bytes per launch = compressed f64
+        # bytes read + 8 B per SELECTED row written (the fused kernel skips the
+        # stores of filtered-out rows; SURVEY.md §8d: count bytes actually
+        # moved).  The unfused number (8 B x all rows) is stated in DESIGN.md.
+        raw_f64_bytes = raw_f64_bytes_sb0 - \
+            (16 + (page_rows + 7) // 8) * (sb_rows // page_rows)
+        sel_rows_sb = int(out_rows) // args.sub_batches
+        alg_bytes_launch = raw_f64_bytes + 8 * sel_rows_sb
+        ms_gorilla_launch = r_cal.ms_decode_val
+        achieved = alg_bytes_launch / (ms_gorilla_launch / 1000) if ms_gorilla_launch > 0 else 0
+        peak = 8.0e12
+        traffic = None
+        pmc_path = os.path.join(REPO, "profiles", "pmc_traffic.json")
+        if os.path.exists(pmc_path):
+            try:
+                pmc = json.load(open(pmc_path))
+                shape = pmc.get("launch_shape", {})
+                # attach only when the PMC collection ran the same launch
+                # shape (a stale half-size traffic number
+                # was attached to a full-size run)
+                if (pmc.get("kernel") == "k_gor_chunks_filtered"
+                        and shape.get("rows_per_launch") == sb_rows
+                        and shape.get("page_rows") == page_rows
+                        and shape.get("sub_batches") == args.sub_batches
+                        and shape.get("series") == nseries):
+                    traffic = pmc.get("bytes_per_launch")
+            except Exception:
+                pass
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": peak,
+                    "unit": "B/s", "frac": achieved / peak, "traffic": traffic}
 
     cpu_baseline = None
-    if rank == 0 and not args.skip_cpu_baseline:
+    if rank == 0 and args.full and not args.skip_cpu_baseline:
         cpu_baseline = cpu_baseline_leg(32, npts, page_rows, lo, hi)
 
     if rank == 0:
@@ -1030,7 +1164,7 @@ def main():
                     "decode_f64": r_cal.ms_decode_val,
                     "filter": r_cal.ms_filter,
                     "agg": r_cal.ms_agg,
-                },
+                } if r_cal is not None else None,
                 "effective_GBps": value * (raw_bytes / (nseries * npts) + 8) / 1e9,
             },
             "roofline": roofline,

@@ -30,6 +30,30 @@ def test_build_workload_pages_parse():
             orc.decode_f64(data, rows)
 
 
+def test_dump_helpers(tmp_path):
+    """--dump-outputs plumbing: the row sample is fixed and seeded, and
+    every array lands as float64 .npy with int64 values kept exact."""
+    import bench
+    assert bench._sample_rows(5).tolist() == [0, 1, 2, 3, 4]
+    n = 10 * bench.DUMP_SAMPLE_ROWS
+    a, b = bench._sample_rows(n), bench._sample_rows(n)
+    assert a.size == bench.DUMP_SAMPLE_ROWS and (a == b).all()
+    assert (np.diff(a) >= 0).all() and a[0] >= 0 and a[-1] < n
+    assert (bench._sample_rows(n, seed=232) != a).any()
+    cnt = np.array([0, 3, 2**40 + 1], dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "out"), {"cnt": cnt,
+                                               "f32": np.ones(3, np.float32)})
+    got = np.load(tmp_path / "out" / "cnt.npy")
+    assert got.dtype == np.float64 and (got.astype(np.int64) == cnt).all()
+    assert np.load(tmp_path / "out" / "f32.npy").dtype == np.float32
+    # empty buckets (count 0) hold the -inf identity; dumped as 0.0, while
+    # buckets with rows are dumped as computed
+    import torch
+    mx = bench._max_for_dump(torch.tensor([-np.inf, 3.5, np.inf]),
+                             torch.tensor([0, 2, 1]))
+    assert mx.tolist() == [0.0, 3.5, np.inf]
+
+
 def test_cpu_baseline_leg_small():
     import bench
     r = bench.cpu_baseline_leg(2, 16000, 4000, bench.T0 + 4000 * bench.NS,
