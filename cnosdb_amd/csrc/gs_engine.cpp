@@ -1698,8 +1698,14 @@ __global__ void k_agg_merge(int ngroups, int nbuckets,
     }
 }
 
-/* Fused-path aggregate partial with CLOSED-FORM bucket boundaries.  The
- * fused scan requires every ts page to be RLE (fused_capable), so the
+/* Fused-path aggregate partial with CLOSED-FORM bucket boundaries, as a
+ * SEPARATE pass over the decoded values.  Since the decode kernel learnt
+ * to aggregate the rows while it holds them (k_gor_chunks_filtered<true> +
+ * k_agg_fixup) this kernel is the fallback: GS_AGG_FUSED=0, buckets below
+ * GS_AGG_FUSED_MIN_ROWS rows, or a set whose piece tables do not fit.  It
+ * re-reads the 8 B/row the decode just wrote and pays a 64-lane shuffle
+ * tree per bucket, which is why it is no longer the default.
+ * The fused scan requires every ts page to be RLE (fused_capable), so the
  * compacted output of each page-group is an affine ts sequence
  * (t0sel + i*delta) recorded by k_spans_rle.  Instead of 1 global binary
  * search over out_ts per bucket boundary (the latency + traffic hot spot
@@ -1807,9 +1813,11 @@ __global__ void k_agg_partial_rle(const DevGroup *__restrict__ sg, int nsg,
             double mx = -__builtin_inf(), sm = 0.0;
             /* 16-B double2 loads: halve the load-instruction traffic of
                the strided 8-B version (the kernel was instruction-bound
-               at 3.4 TB/s vs the ~6.3 achievable).  Output buffers are
-               16-B aligned; an odd start row is peeled. */
-            const int head = int((base + s) & 1);
+               at 3.4 TB/s vs the ~6.3 achievable).  A start row that is
+               not 16-B aligned is peeled; the peel goes by the address,
+               not the row index, since field f of a multi-field scan
+               starts at f*total_rows, odd for an odd total. */
+            const int head = int((uintptr_t(v + s) >> 3) & 1);
             if (head && lane == 0) {
                 double x = v[s];
                 mx = x;
@@ -2501,10 +2509,10 @@ __global__ void k_rle_ts_filtered(const uint8_t *__restrict__ blob,
         int64_t *o = out_ts + out_off[pg.grp];
         /* paired 16-B stores: closed-form generation is pure store
            bandwidth; halving the store-instruction count lifted the
-           measured rate (output buffers are 16-B aligned; out_off parity
-           decides the 1-row peel) */
+           measured rate (the 1-row peel goes by the destination address,
+           so a caller's 8-B-aligned buffer is as good as a 16-B one) */
         const uint64_t base = uint64_t(first) + uint64_t(st) * uint64_t(delta);
-        const int64_t head = (out_off[pg.grp] & 1) ? 1 : 0;
+        const int64_t head = int64_t((uintptr_t(o) >> 3) & 1);
         if (head && threadIdx.x == 0 && cnt > 0) o[0] = int64_t(base);
         const int64_t n2 = (cnt - head) >> 1;
         longlong2 *op = (longlong2 *)(o + head);
@@ -2525,13 +2533,17 @@ __global__ void k_rle_ts_filtered(const uint8_t *__restrict__ blob,
  * analog of the reference's page min/max pruning, reader/chunk.rs:12-49 —
  * a chunk wholly outside the time range is never parsed at all).  Output
  * order is wave-compacted (near table order); chunks write disjoint
- * output rows so order never affects results. */
+ * output rows so order never affects results.  With the fused aggregate
+ * (pieces != nullptr) a chunk left out of the list gets its two piece
+ * slots marked absent here, so nothing survives from an earlier scan with
+ * another time range. */
 __global__ void k_gor_active(const DevGorChunk *__restrict__ chunks,
                              int nchunks,
                              const int64_t *__restrict__ sp_start,
                              const int64_t *__restrict__ sp_cnt,
                              int *__restrict__ active,
-                             int *__restrict__ n_active) {
+                             int *__restrict__ n_active,
+                             DevAggMeta *__restrict__ pieces) {
     const int lane = threadIdx.x & 63;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nchunks;
          i += gridDim.x * blockDim.x) {
@@ -2541,6 +2553,12 @@ __global__ void k_gor_active(const DevGorChunk *__restrict__ chunks,
         int64_t lo = sp_start[grp];
         int64_t hi = lo + sp_cnt[grp];
         bool act = row0 < hi && rend > lo;
+        if (pieces && !act) {
+            uint32_t slot = chunks[i].slot;
+            if (slot != GOR_NO_SLOT) /* both pieces: one 16-B store */
+                *(int4 *)(pieces + 2 * size_t(slot)) =
+                    make_int4(AGG_NO_PIECE, 0, AGG_NO_PIECE, 0);
+        }
         uint64_t m = __ballot(act);
         if (m) {
             int leader = __ffsll((unsigned long long)m) - 1;
@@ -2558,7 +2576,46 @@ __global__ void k_gor_active(const DevGorChunk *__restrict__ chunks,
  * in the output by construction).  Runs over the k_gor_active index list;
  * rows before the span are parsed but not staged (the bitstream is
  * sequential), and a chunk whose decodability was proven by the upload
- * pre-pass (safe_stop) stops as soon as the span's end is passed. */
+ * pre-pass (safe_stop) stops as soon as the span's end is passed.
+ *
+ * AGG = true also aggregates the staged rows into the scan's time buckets
+ * while they sit in the lane's registers, so no later kernel has to read
+ * the 8 B/row it just wrote.  A page's ts is first + r*delta, so the row
+ * at which bucket k starts is ceil((t0 + k*bucket_ns - first) / delta):
+ * two wide divisions per chunk at init, then each further boundary by
+ * adding bucket_ns/delta and carrying the remainder (no division in the
+ * row loop).  A lane keeps a running max/sum of the current piece; at a
+ * boundary the finished piece goes to the chunk's head slot if it is the
+ * chunk's first, else straight into its (sgroup, bucket) cell — a bucket
+ * strictly inside one chunk's rows is complete for the series.  The last
+ * piece goes to the tail slot (DevAggMeta/DevAggVal; k_agg_fixup).  Rows before t0
+ * accumulate into pseudo bucket -1 and rows past the grid into bucket
+ * n_buckets; neither is ever stored as a cell. */
+struct GorAggArgs {
+    const int32_t *grp_sg;  /* page-group -> series group */
+    const int64_t *g_t0sel; /* k_spans_rle: ts of first selected row */
+    const int64_t *g_delta; /* k_spans_rle: RLE delta */
+    int64_t t0, bucket_ns;
+    int nbuckets;
+    double *pmax, *psum;
+    long long *pcnt;
+    DevAggMeta *pc_meta; /* [2*slot], [2*slot+1]: head, tail */
+    DevAggVal *pc_val;
+};
+
+/* Fewest rows a bucket must span (bucket_ns / smallest positive RLE delta
+ * of the set) for the fused aggregate to be chosen; below it the scan
+ * launches k_agg_partial_rle as before.  Measured on MI355X, 16384 series
+ * x 3 pages x 4500 rows, middle half selected, decode+aggregate ms of one
+ * scan (fused / separate): 300 rows per bucket 2.94 / 2.98, 64: 2.99 /
+ * 3.40, 16: 3.35 / 5.16, 8: 4.07 / 7.61, 4: 5.83 / 12.6, 2: 9.28 / 22.9.
+ * A boundary costs no division here, and the separate pass pays a 64-lane
+ * shuffle tree per bucket, so no crossover was found: the fused path led
+ * at every size measured.  Below 2 rows per bucket nothing was measured
+ * (n_buckets > 8192 at that shape), so that range keeps the old path. */
+#define GS_AGG_FUSED_MIN_ROWS 2
+
+template <bool AGG>
 __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
                                       const DevGorChunk *__restrict__ chunks,
                                       const int *__restrict__ active,
@@ -2567,7 +2624,8 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
                                       const int64_t *__restrict__ sp_cnt,
                                       const int64_t *__restrict__ out_off,
                                       double *__restrict__ out,
-                                      unsigned *__restrict__ err) {
+                                      unsigned *__restrict__ err,
+                                      GorAggArgs ag) {
     __shared__ double ring[GS_GOR_BLOCK / 64][GS_RING][64 + 1];
     /* per-flush lane descriptors: {dst pointer, staged count} packed so the
        flush loop reads ONE broadcast ds_read per source lane instead of
@@ -2600,6 +2658,78 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
         int32_t run0 = 0; /* output row of first staged entry */
         bool done = !have, over = false, clean_stop = false;
         if (have && st.bad) { atomicOr(err, DERR_SHORT); done = true; }
+        /* AGG: current piece = rows [a_start, r) of bucket a_b; a_next is
+           the page-local row at which bucket a_b+1 starts, a_slack how far
+           (ns) that row lies past the boundary itself */
+        int32_t a_b = -1, a_next = INT32_MAX, a_start = 0;
+        double a_mx = -__builtin_inf(), a_sm = 0.0;
+        uint64_t a_slack = 0, a_rem = 0, a_d = 0;
+        uint32_t a_q = 0;
+        size_t a_cell0 = 0;
+        bool a_head = false; /* the chunk's head slot has been written */
+        if (AGG && have) {
+            const int64_t d = ag.g_delta[ch.grp];
+            const int32_t rs = r > sel_lo ? r : sel_lo; /* first staged row */
+            a_start = rs;
+            a_cell0 = size_t(ag.grp_sg[ch.grp]) * size_t(ag.nbuckets);
+            /* ts of row rs relative to the grid origin */
+            const __int128 x = (__int128)ag.g_t0sel[ch.grp] +
+                               (__int128)(rs - sel_lo) * d - ag.t0;
+            __int128 kb = x < 0 ? -1 : x / ag.bucket_ns;
+            if (kb > ag.nbuckets) kb = ag.nbuckets;
+            a_b = int32_t(kb);
+            if (d > 0 && a_b < ag.nbuckets) {
+                /* ns from row rs to the start of bucket a_b+1: > 0 */
+                const __int128 bound = (__int128)(a_b + 1) * ag.bucket_ns - x;
+                const __int128 k = (bound + d - 1) / d; /* rows, >= 1 */
+                a_slack = uint64_t(k * d - bound);
+                a_next = rs + k > INT32_MAX ? INT32_MAX : int32_t(rs + k);
+                const uint64_t q = uint64_t(ag.bucket_ns) / uint64_t(d);
+                a_q = q > INT32_MAX ? uint32_t(INT32_MAX) : uint32_t(q);
+                a_rem = uint64_t(ag.bucket_ns) % uint64_t(d);
+                a_d = uint64_t(d);
+            }
+        }
+        auto agg_put = [&](size_t pi, int32_t cnt) {
+            DevAggVal v;
+            v.mx = a_mx;
+            v.sm = a_sm;
+            ag.pc_val[pi] = v;
+            DevAggMeta m;
+            m.bucket = a_b;
+            m.cnt = cnt;
+            ag.pc_meta[pi] = m;
+        };
+        /* row r opens the next bucket: the piece that ends here is not the
+           chunk's last, so it is the head or complete.  Loops only when a
+           bucket is shorter than the row spacing (empty complete cells). */
+        auto agg_boundary = [&]() {
+            do {
+                const int32_t cnt = r - a_start;
+                if (!a_head) {
+                    agg_put(2 * size_t(ch.slot), cnt);
+                    a_head = true;
+                } else if (a_b >= 0) { /* a_b < nbuckets: else a_next is
+                                          INT32_MAX and never reached */
+                    const size_t cell = a_cell0 + size_t(a_b);
+                    ag.pmax[cell] = a_mx;
+                    ag.psum[cell] = a_sm;
+                    ag.pcnt[cell] = cnt;
+                }
+                a_b++;
+                a_start = r;
+                a_mx = -__builtin_inf();
+                a_sm = 0.0;
+                if (a_b >= ag.nbuckets) {
+                    a_next = INT32_MAX;
+                } else {
+                    int64_t nn = int64_t(a_next) + int64_t(a_q);
+                    if (a_slack < a_rem) { a_slack += a_d; nn++; }
+                    a_slack -= a_rem;
+                    a_next = nn > INT32_MAX ? INT32_MAX : int32_t(nn);
+                }
+            } while (a_next == r);
+        };
         auto topup = [&]() { /* only with nb < 64 */
             uint64_t x = st.nextw;
             st.nextw = st.nextw2;
@@ -2652,6 +2782,12 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
         };
         auto stage_row = [&](uint64_t bits_) {
             if (r >= sel_lo && r < sel_hi) {
+                if (AGG) {
+                    if (r == a_next) agg_boundary();
+                    const double x = __longlong_as_double((long long)bits_);
+                    if (x > a_mx) a_mx = x;
+                    a_sm += x;
+                }
                 if (rfill == 0) run0 = r;
                 *rcur = __longlong_as_double((long long)bits_);
                 rcur += 65;
@@ -2728,6 +2864,98 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
         }
         flush();
         if (have && r < end && !clean_stop) atomicOr(err, DERR_SHORT);
+        if (AGG && have) {
+            /* the open piece is the chunk's last: its only one (head, no
+               tail) or its tail.  Every active chunk writes both slots. */
+            const int32_t e = r < sel_hi ? r : sel_hi;
+            const int32_t cnt = e > a_start ? e - a_start : 0;
+            const size_t pi = 2 * size_t(ch.slot);
+            if (!a_head) {
+                agg_put(pi, cnt);
+                DevAggMeta none;
+                none.bucket = AGG_NO_PIECE;
+                none.cnt = 0;
+                ag.pc_meta[pi + 1] = none;
+            } else {
+                agg_put(pi + 1, cnt);
+            }
+        }
+    }
+}
+
+/* Fused aggregate, second half: one block per series group walks the
+ * group's chunk pieces in slot order (page-group order, then row order =
+ * time order, as k_agg_partial_rle assumes too) and folds head and tail
+ * pieces that share a bucket, always in that order, so the sum has one
+ * fixed association however the decode lanes were scheduled.  Each such
+ * cell is written once, by the thread that owns the first piece of its
+ * run.  Cells the decode kernel completed itself — the buckets strictly
+ * between a chunk's head and tail — are only marked; every cell left
+ * unmarked received no rows and gets (-inf, 0.0, 0).  After this kernel
+ * every (sgroup, bucket) cell holds this scan's value, by plain stores. */
+__global__ void k_agg_fixup(const DevAggMeta *__restrict__ pc_meta,
+                            const DevAggVal *__restrict__ pc_val,
+                            const int32_t *__restrict__ sg_chunk_first,
+                            int nsg, int nbuckets, int max_pieces,
+                            double *__restrict__ pmax,
+                            double *__restrict__ psum,
+                            long long *__restrict__ pcnt) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    int32_t *pb = (int32_t *)smem;            /* [max_pieces] bucket or -1 */
+    uint8_t *done = smem + size_t(max_pieces) * 4; /* [nbuckets] */
+    for (int g = blockIdx.x; g < nsg; g += gridDim.x) {
+        const int c0 = sg_chunk_first[g];
+        const int nch = sg_chunk_first[g + 1] - c0;
+        const int np = 2 * nch;
+        const DevAggMeta *gm = pc_meta + 2 * size_t(c0);
+        const DevAggVal *gv = pc_val + 2 * size_t(c0);
+        const size_t cell0 = size_t(g) * size_t(nbuckets);
+        for (int b = threadIdx.x; b < nbuckets; b += blockDim.x) done[b] = 0;
+        __syncthreads();
+        for (int c = threadIdx.x; c < nch; c += blockDim.x) {
+            const int4 ht = *(const int4 *)(gm + 2 * c);
+            const int32_t hb = ht.x, hc = ht.y, tb = ht.z, tc = ht.w;
+            const bool hok = hb >= 0 && hb < nbuckets && hc > 0;
+            const bool tok = tb >= 0 && tb < nbuckets && tc > 0;
+            pb[2 * c] = hok ? hb : -1;
+            pb[2 * c + 1] = tok ? tb : -1;
+            if (hb != AGG_NO_PIECE && tb != AGG_NO_PIECE) {
+                const int lo = hb + 1 > 0 ? hb + 1 : 0;
+                const int hi = tb < nbuckets ? tb : nbuckets;
+                for (int b = lo; b < hi; b++) done[b] = 1;
+            }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < np; i += blockDim.x) {
+            const int32_t b = pb[i];
+            if (b < 0) continue;
+            int j = i - 1;
+            while (j >= 0 && pb[j] < 0) j--;
+            if (j >= 0 && pb[j] == b) continue; /* continues an earlier run */
+            double mx = gv[i].mx, sm = gv[i].sm;
+            long long c = gm[i].cnt;
+            for (int k = i + 1; k < np; k++) {
+                const int32_t bk = pb[k];
+                if (bk < 0) continue;
+                if (bk != b) break;
+                const double omx = gv[k].mx;
+                if (omx > mx) mx = omx;
+                sm += gv[k].sm;
+                c += gm[k].cnt;
+            }
+            pmax[cell0 + b] = mx;
+            psum[cell0 + b] = sm;
+            pcnt[cell0 + b] = c;
+            done[b] = 1;
+        }
+        __syncthreads();
+        for (int b = threadIdx.x; b < nbuckets; b += blockDim.x)
+            if (!done[b]) {
+                pmax[cell0 + b] = -__builtin_inf();
+                psum[cell0 + b] = 0.0;
+                pcnt[cell0 + b] = 0;
+            }
+        __syncthreads();
     }
 }
 
@@ -3061,6 +3289,15 @@ struct SlotPages {
     DevGorChunk *d_gorn_chunks = nullptr;
     int n_gorn_chunks = 0;
     int32_t *d_gorn_chunk_base = nullptr; /* [n[PC_GORN]+1] */
+    /* fused aggregate (PC_GOR): DevGorChunk.slot ordinal of each
+       page-group's first chunk, and from it the series groups' slot
+       ranges.  agg_fused_ok: every page-group has exactly one PC_GOR page
+       in this slot and every chunk a slot, so a series group's pieces are
+       one contiguous, time-ordered slot range. */
+    std::vector<int32_t> gor_grp_cbase;  /* [ngroups+1] */
+    int32_t *d_sg_chunk_first = nullptr; /* [nsgroups+1] */
+    int max_sg_chunks = 0;
+    bool agg_fused_ok = false;
 };
 
 struct GsGroupSet {
@@ -3097,6 +3334,15 @@ struct GsGroupSet {
     int *d_gor_active = nullptr;
     int *d_gor_nactive = nullptr;
     size_t gor_active_cap = 0;
+    /* fused aggregate: page-group -> series group, the per-chunk head/tail
+       pieces (lazy; two per chunk of the largest slot, reused from field
+       to field like the partial cells), and the smallest positive RLE
+       delta of the time pages (INT64_MAX if none) for the gate */
+    int32_t *d_grp_sgroup = nullptr;
+    DevAggMeta *d_agg_meta = nullptr;
+    DevAggVal *d_agg_val = nullptr;
+    size_t agg_pieces_cap = 0;
+    int64_t min_pos_delta = INT64_MAX;
     /* string decode scratch (lazy, cached across gs_decode_str calls) */
     uint8_t *d_str_scratch = nullptr;
     size_t str_scratch_cap = 0;
@@ -3358,6 +3604,23 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
         } else if (hp.dp.all_valid && hp.dp.sub == 2 && int_ct && hp.dp.data_len > 2) {
             if (hp.dp.enc == GS_ENC_DELTATS) cls = PC_RLE_TS;
             else if (hp.dp.enc == GS_ENC_DELTA) cls = PC_RLE_I64;
+            if (cls == PC_RLE_TS && hp.col == 0 && hp.dp.data_len > 10) {
+                /* RLE delta as k_spans_rle reads it: [enc][sub|log10
+                   scale][first BE64][varint delta]... */
+                uint64_t scaler = 1, dv = 0;
+                for (unsigned k = 0; k < (hp.data_src[1] & 0x0fu); k++)
+                    scaler *= 10;
+                int sh = 0;
+                for (uint32_t i = 10; i < hp.dp.data_len && sh < 64; i++) {
+                    uint8_t b = hp.data_src[i];
+                    dv |= uint64_t(b & 0x7f) << sh;
+                    sh += 7;
+                    if (!(b & 0x80)) break;
+                }
+                int64_t delta = int64_t(dv * scaler);
+                if (delta > 0 && delta < set->min_pos_delta)
+                    set->min_pos_delta = delta;
+            }
         } else if (hp.dp.all_valid && hp.dp.sub == 1 && int_ct &&
                    (hp.dp.enc == GS_ENC_DELTATS || hp.dp.enc == GS_ENC_DELTA) &&
                    hp.dp.data_len > 2) {
@@ -3417,11 +3680,25 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
             std::vector<int32_t> cbase(sp.n[pc] + 1);
             std::vector<DevGorChunk> hch;
             int32_t acc = 0;
+            auto nch_of = [&](const DevPage &pg) {
+                return pg.nrows ? (pg.nrows + chunk_rows - 1) / chunk_rows
+                                : 1u;
+            };
+            if (gcls == 0) {
+                /* chunk ordinals in page-group order (the table below is
+                   sorted by page length): DevGorChunk.slot */
+                sp.gor_grp_cbase.assign(ngroups + 1, 0);
+                for (int i = 0; i < sp.n[pc]; i++)
+                    sp.gor_grp_cbase[sp.host[pc][i].grp + 1] +=
+                        int32_t(nch_of(sp.host[pc][i]));
+                for (size_t g = 0; g < ngroups; g++)
+                    sp.gor_grp_cbase[g + 1] += sp.gor_grp_cbase[g];
+                sp.agg_fused_ok = sp.n[pc] == int(ngroups);
+            }
             for (int i = 0; i < sp.n[pc]; i++) {
                 const DevPage &pg = sp.host[pc][i];
                 cbase[i] = acc;
-                uint32_t nch =
-                    pg.nrows ? (pg.nrows + chunk_rows - 1) / chunk_rows : 1;
+                uint32_t nch = nch_of(pg);
                 for (uint32_t k = 0; k < nch; k++) {
                     DevGorChunk c{};
                     c.data_off = pg.data_off;
@@ -3436,6 +3713,9 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
                     c.data_len = pg.data_len;
                     c.meaningful = 64;
                     c.last = uint8_t(k == nch - 1);
+                    c.slot = gcls == 0
+                                 ? uint32_t(sp.gor_grp_cbase[pg.grp]) + k
+                                 : GOR_NO_SLOT;
                     hch.push_back(c);
                 }
                 acc += int32_t(nch);
@@ -3459,7 +3739,11 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
                 if (maxc > 1) {
                     il_stride = sp.n[pc];
                     std::vector<DevGorChunk> h2(size_t(maxc) * sp.n[pc]);
-                    for (auto &c : h2) { c = DevGorChunk{}; c.cnt = 0; }
+                    for (auto &c : h2) {
+                        c = DevGorChunk{};
+                        c.cnt = 0;
+                        c.slot = GOR_NO_SLOT;
+                    }
                     for (int i = 0; i < sp.n[pc]; i++) {
                         int nchi = cbase[i + 1] - cbase[i];
                         for (int k = 0; k < nchi; k++)
@@ -3563,6 +3847,48 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
                    ctx->stream);
     hipMemcpyAsync(set->d_groups, hg.data(), ngroups * sizeof(DevGroup),
                    hipMemcpyHostToDevice, ctx->stream);
+    /* fused-aggregate tables: page-group -> series group, and per Gorilla
+       slot the series groups' ranges of chunk ordinals.  Page-groups of a
+       series group are consecutive and the ordinals run in page-group
+       order, so each range is contiguous by construction; checked anyway,
+       and a slot that fails keeps the separate aggregate kernel. */
+    std::vector<int32_t> grp_sg(ngroups);
+    for (size_t s = 0; s < hsg.size(); s++)
+        for (int32_t g = sgfirst[s]; g < sgfirst[s + 1]; g++)
+            grp_sg[g] = int32_t(s);
+    std::vector<std::vector<int32_t>> sgc(ncols);
+    if (hipMalloc(&set->d_grp_sgroup, ngroups * sizeof(int32_t)) != hipSuccess) {
+        fail(GS_ERR, "hipMalloc group->sgroup table failed");
+        gs_groups_free(set); return nullptr;
+    }
+    hipMemcpyAsync(set->d_grp_sgroup, grp_sg.data(),
+                   ngroups * sizeof(int32_t), hipMemcpyHostToDevice,
+                   ctx->stream);
+    for (uint32_t c = 0; c < ncols; c++) {
+        SlotPages &sp = set->slots[c];
+        if (!sp.agg_fused_ok) continue;
+        std::vector<int32_t> &t = sgc[c];
+        t.resize(hsg.size() + 1);
+        for (size_t s = 0; s <= hsg.size(); s++)
+            t[s] = sp.gor_grp_cbase[sgfirst[s]];
+        /* (the interleaved layout experiment pads the table, so the
+           ordinals may number fewer than n_gor_chunks, never more) */
+        if (t[0] != 0 || t[hsg.size()] > sp.n_gor_chunks)
+            sp.agg_fused_ok = false;
+        for (size_t s = 0; s < hsg.size() && sp.agg_fused_ok; s++) {
+            if (t[s + 1] < t[s]) sp.agg_fused_ok = false;
+            if (t[s + 1] - t[s] > sp.max_sg_chunks)
+                sp.max_sg_chunks = t[s + 1] - t[s];
+        }
+        if (!sp.agg_fused_ok) continue;
+        if (hipMalloc(&sp.d_sg_chunk_first, t.size() * sizeof(int32_t)) != hipSuccess) {
+            fail(GS_ERR, "hipMalloc sgroup chunk table failed");
+            gs_groups_free(set); return nullptr;
+        }
+        hipMemcpyAsync(sp.d_sg_chunk_first, t.data(),
+                       t.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                       ctx->stream);
+    }
     HIP_TRY_NULL(hipStreamSynchronize(ctx->stream));
     return set;
 }
@@ -3579,7 +3905,11 @@ void gs_groups_free(GsGroupSet *set) {
         if (sp.d_gor_chunk_base) hipFree(sp.d_gor_chunk_base);
         if (sp.d_gorn_chunks) hipFree(sp.d_gorn_chunks);
         if (sp.d_gorn_chunk_base) hipFree(sp.d_gorn_chunk_base);
+        if (sp.d_sg_chunk_first) hipFree(sp.d_sg_chunk_first);
     }
+    if (set->d_grp_sgroup) hipFree(set->d_grp_sgroup);
+    if (set->d_agg_meta) hipFree(set->d_agg_meta);
+    if (set->d_agg_val) hipFree(set->d_agg_val);
     if (set->d_gor_active) hipFree(set->d_gor_active);
     if (set->d_gor_nactive) hipFree(set->d_gor_nactive);
     if (set->d_str_scratch) hipFree(set->d_str_scratch);
@@ -4185,26 +4515,98 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
         double *d_val_f = spec->d_out_val + size_t(f) * set->total_rows;
         HIP_TRY(hipMemsetAsync(set->d_gor_nactive, 0, sizeof(int),
                                ctx->stream));
+        /* closed-form bucket boundaries via the RLE group table when it
+           fits in LDS (it always does for realistic pages-per-series) */
+        const size_t shm_rle =
+            size_t(set->max_span) * 16 +
+            (size_t(set->max_span) + size_t(spec->n_buckets) + 2) * 4;
+        const bool rle_fits =
+            spec->n_buckets <= 8192 && shm_rle <= 64 * 1024;
+        /* Fused aggregate: the decode kernel accumulates the buckets and
+           k_agg_fixup joins the pieces, in place of k_agg_partial_rle's
+           second pass over the decoded values.  Each bucket boundary
+           costs the decoding wave a divergent branch with three stores,
+           so a bucket must span enough rows to pay for it. */
+        const size_t shm_fix =
+            (size_t(fsp.max_sg_chunks) * 2 * 4 + size_t(spec->n_buckets) +
+             15) & ~size_t(15);
+        bool agg_fused = false;
+        if (spec->n_buckets > 0 && rle_fits && fsp.agg_fused_ok &&
+            spec->bucket_ns > 0 && shm_fix <= 64 * 1024) {
+            static int fused_env = [] { /* GS_AGG_FUSED=0: separate pass */
+                const char *e = getenv("GS_AGG_FUSED");
+                return e ? atoi(e) : 1;
+            }();
+            static long min_rows = [] { /* sweepable */
+                const char *e = getenv("GS_AGG_FUSED_MIN_ROWS");
+                long v = e ? atol(e) : 0;
+                return v > 0 ? v : long(GS_AGG_FUSED_MIN_ROWS);
+            }();
+            agg_fused = fused_env != 0 &&
+                        (set->min_pos_delta == INT64_MAX ||
+                         spec->bucket_ns / set->min_pos_delta >= min_rows);
+        }
+        if (agg_fused && set->agg_pieces_cap < size_t(nch_max) * 2) {
+            if (set->d_agg_meta) hipFree(set->d_agg_meta);
+            if (set->d_agg_val) hipFree(set->d_agg_val);
+            set->d_agg_meta = nullptr;
+            set->d_agg_val = nullptr;
+            set->agg_pieces_cap = 0;
+            if (hipMalloc(&set->d_agg_meta, size_t(nch_max) * 2 *
+                                                sizeof(DevAggMeta)) !=
+                    hipSuccess ||
+                hipMalloc(&set->d_agg_val, size_t(nch_max) * 2 *
+                                               sizeof(DevAggVal)) !=
+                    hipSuccess)
+                return fail(GS_ERR, "hipMalloc agg pieces failed");
+            set->agg_pieces_cap = size_t(nch_max) * 2;
+        }
         hipLaunchKernelGGL(k_gor_active, dim3(grid_for(nch, 256)), dim3(256),
                            0, ctx->stream, fsp.d_gor_chunks, nch,
                            set->d_sp_start, set->d_sp_cnt, set->d_gor_active,
-                           set->d_gor_nactive);
-        hipLaunchKernelGGL(k_gor_chunks_filtered,
-                           dim3(grid_for(nch, GS_GOR_BLOCK)),
-                           dim3(GS_GOR_BLOCK), 0, ctx->stream, set->d_blob,
-                           fsp.d_gor_chunks, set->d_gor_active,
-                           set->d_gor_nactive, set->d_sp_start,
-                           set->d_sp_cnt, set->d_out_off, d_val_f,
-                           ctx->d_err);
+                           set->d_gor_nactive,
+                           agg_fused ? set->d_agg_meta : nullptr);
+        GorAggArgs ag{};
+        if (agg_fused) {
+            ag.grp_sg = set->d_grp_sgroup;
+            ag.g_t0sel = set->d_g_t0sel;
+            ag.g_delta = set->d_g_delta;
+            ag.t0 = spec->t0;
+            ag.bucket_ns = spec->bucket_ns;
+            ag.nbuckets = spec->n_buckets;
+            ag.pmax = set->d_pmax;
+            ag.psum = set->d_psum;
+            ag.pcnt = set->d_pcnt;
+            ag.pc_meta = set->d_agg_meta;
+            ag.pc_val = set->d_agg_val;
+            hipLaunchKernelGGL(k_gor_chunks_filtered<true>,
+                               dim3(grid_for(nch, GS_GOR_BLOCK)),
+                               dim3(GS_GOR_BLOCK), 0, ctx->stream,
+                               set->d_blob, fsp.d_gor_chunks,
+                               set->d_gor_active, set->d_gor_nactive,
+                               set->d_sp_start, set->d_sp_cnt,
+                               set->d_out_off, d_val_f, ctx->d_err, ag);
+        } else {
+            hipLaunchKernelGGL(k_gor_chunks_filtered<false>,
+                               dim3(grid_for(nch, GS_GOR_BLOCK)),
+                               dim3(GS_GOR_BLOCK), 0, ctx->stream,
+                               set->d_blob, fsp.d_gor_chunks,
+                               set->d_gor_active, set->d_gor_nactive,
+                               set->d_sp_start, set->d_sp_cnt,
+                               set->d_out_off, d_val_f, ctx->d_err, ag);
+        }
         if (f == 0) HIP_TRY(hipEventRecord(ev[3], ctx->stream));
         if (spec->n_buckets > 0) {
-            /* closed-form boundaries via the RLE group table when it
-               fits in LDS (it always does for realistic pages-per-
-               series); otherwise the out_ts binary-search kernel */
-            size_t shm_rle =
-                size_t(set->max_span) * 16 +
-                (size_t(set->max_span) + size_t(spec->n_buckets) + 2) * 4;
-            if (spec->n_buckets <= 8192 && shm_rle <= 64 * 1024) {
+            if (agg_fused) {
+                hipLaunchKernelGGL(k_agg_fixup,
+                                   dim3(nsg > 65535 ? 65535 : nsg),
+                                   dim3(256), shm_fix, ctx->stream,
+                                   set->d_agg_meta, set->d_agg_val,
+                                   fsp.d_sg_chunk_first,
+                                   nsg, spec->n_buckets,
+                                   fsp.max_sg_chunks * 2, set->d_pmax,
+                                   set->d_psum, set->d_pcnt);
+            } else if (rle_fits) {
                 static int agg_block = [] { /* sweepable (GS_AGG_BLOCK) */
                     const char *e = getenv("GS_AGG_BLOCK");
                     long v = e ? atol(e) : 0;
@@ -4247,6 +4649,13 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
     return GS_OK;
 }
 
+/* Phase times from the six events of scan_fused_launch: filter = spans +
+ * offset scan, decode_ts = k_rle_ts_filtered, decode_val = k_gor_active +
+ * the Gorilla decode of field 0, agg = everything after it.  With the
+ * fused aggregate (GS_AGG_FUSED, the default where the gate passes)
+ * decode_val includes the in-kernel bucket accumulation and agg covers
+ * only k_agg_fixup + k_agg_merge; on the separate path agg is
+ * k_agg_partial_rle (or k_agg_partial) + k_agg_merge as before. */
 static GsStatus scan_fused_wait(GsCtx *ctx, GsGroupSet *set,
                                 GsScanResult *result) {
     if (!set->pending)
@@ -4268,7 +4677,8 @@ static GsStatus scan_fused_wait(GsCtx *ctx, GsGroupSet *set,
     result->ms_decode_val = ms; /* nf>1: field 0 only */
     result->ms_compact = 0.0;
     HIP_TRY(hipEventElapsedTime(&ms, ev[3], ev[4]));
-    result->ms_agg = ms; /* nf>1: field 0's agg + remaining fields */
+    result->ms_agg = ms; /* fused aggregate: fix-up + merge only.
+                            nf>1: field 0's agg + remaining fields */
     result->out_rows = acc;
     result->decoded_rows = set->total_rows;
     return GS_OK;

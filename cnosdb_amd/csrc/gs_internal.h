@@ -65,7 +65,32 @@ struct DevGorChunk {
     uint8_t meaningful;
     uint8_t last;        /* final chunk: page-end semantics (sentinel) */
     uint8_t flags;       /* GORF_* */
+    uint32_t slot;       /* PC_GOR: chunk ordinal in PAGE-GROUP order (the
+                            table itself is sorted longest-page-first), the
+                            index of this chunk's head/tail aggregate pieces;
+                            GOR_NO_SLOT for padding entries and PC_GORN.
+                            Occupies former tail padding: sizeof stays 64. */
 };
+#define GOR_NO_SLOT 0xffffffffu
+
+/* Fused decode+aggregate: the run of selected rows a chunk decodes splits
+ * into one piece per bucket it touches.  The first (head) and last (tail)
+ * piece may continue in the neighbouring chunk or page, so they are parked
+ * here, two per chunk at [2*slot] and [2*slot+1], and k_agg_fixup combines
+ * them in slot order.  bucket is the raw grid index, which may lie outside
+ * [0, n_buckets) for rows off the grid; AGG_NO_PIECE marks "no such piece"
+ * (inactive chunk, or a chunk whose rows stay in one bucket has no tail).
+ * Two arrays, so that marking a chunk's pieces absent is one 16-B store
+ * and the fix-up's bucket scan reads only the small half. */
+struct DevAggMeta {
+    int32_t bucket;
+    int32_t cnt;
+};
+struct DevAggVal {
+    double mx;
+    double sm;
+};
+#define AGG_NO_PIECE INT32_MIN
 
 /* launch-class partition of a column slot's pages */
 enum PageClass {
