@@ -2347,6 +2347,278 @@ __global__ void k_cm_scatter(CompactArgs a, int nsets, int nseries,
     }
 }
 
+/* ---- multi-column scatter (gs_compact_merge_fields) ----
+ * A column group is a time column plus every field column of the table;
+ * BatchMergeBuilder::take_last_and_merge (batch_builder.rs:132-155)
+ * resolves each column independently over the rows sharing a timestamp:
+ * per column the newest non-null value wins.  Owner flags and prefixes
+ * depend on timestamps only, so k_cm_flags/k_cm_prefix run once for any
+ * ncols; only the scatter differs.
+ *
+ * The (stream x column) pointer table is up to 16*32*2 pointers — too big
+ * for a by-value argument, so it lives in device memory:
+ *   val[f*ncols+c], valid[f*ncols+c]  (NULL val = column absent in f,
+ *   NULL valid = all rows valid), out_val[c], out_valid[c]. */
+struct CompactFieldsArgs {
+    CompactArgs m;               /* val/valid unused here */
+    const void *const *val;      /* device [nsets*ncols] */
+    const uint8_t *const *valid; /* device [nsets*ncols] */
+    void *const *out_val;        /* device [ncols] */
+    uint8_t *const *out_valid;   /* device [ncols], entries may be NULL */
+    uint32_t wide;               /* bit c set: 8-byte column, else 1-byte */
+    int32_t ncols;
+};
+
+/* raw-bit move of one cell; no arithmetic touches a value */
+__device__ __forceinline__ void cm_move_cell(void *dst, int64_t dpos,
+                                             const void *src, int64_t srow,
+                                             bool wide) {
+    if (wide)
+        ((uint64_t *)dst)[dpos] = ((const uint64_t *)src)[srow];
+    else
+        ((uint8_t *)dst)[dpos] = ((const uint8_t *)src)[srow];
+}
+
+/* Same tiling as k_cm_scatter (CM_TILE stream-f elements, 8 per lane; the
+ * window of every other stream staged once in LDS).  A lane cannot hold
+ * ncols x 8 pending values, so values resolve against the final position:
+ *   1. rank pass over all other streams -> pos; older-stream hits are
+ *      kept as a 16-bit mask per element
+ *   2. the owner stores out_ts and its own stream's valid columns; the
+ *      rest (null or absent in f) form a 32-bit unresolved mask
+ *   3. walk-back f-1 .. 0: a block vote skips streams (and, for
+ *      all-valid data, the whole step) that no unresolved element hits;
+ *      on a hit every unresolved column valid there is stored straight
+ *      to out[c][pos] and its bit cleared
+ *   4. leftovers get the zero value and validity 0.
+ * Every output cell is stored exactly once, in a fixed order, with plain
+ * stores.  Per-lane arrays are only ever indexed by unrolled constants
+ * (a done-mask replaces k_cm_scatter's running index), so they stay in
+ * VGPRs: no scratch. */
+__global__ void __launch_bounds__(256)
+k_cm_scatter_fields(CompactFieldsArgs a, int nsets, int nseries,
+                    int64_t *__restrict__ out_ts) {
+    constexpr int NE = CM_TILE / 256;
+    __shared__ int64_t wts[CM_W];
+    __shared__ int32_t wpf[CM_W];
+    __shared__ uint8_t wfl[CM_W];
+    __shared__ int64_t wb_sh[2];
+    const int f = blockIdx.y;
+    const int ncols = a.ncols;
+    for (int s = blockIdx.x; s < nseries; s += gridDim.x) {
+        const DevGroup g = a.m.groups[f][s];
+        const int64_t *t = a.m.ts[f] + g.row_off;
+        const uint8_t *fl = a.m.flags[f] + g.row_off;
+        const int32_t *pf = a.m.prefix[f] + g.row_off;
+        const int64_t base = a.m.out_off[s];
+        for (int64_t j0 = 0; j0 < g.nrows; j0 += CM_TILE) {
+            const int64_t je = j0 + CM_TILE < g.nrows ? j0 + CM_TILE
+                                                      : g.nrows;
+            int64_t x[NE], pos[NE];
+            uint32_t unres[NE];
+            uint16_t hit[NE];
+            uint32_t ownm = 0; /* bit i: element i exists and owns its row */
+#pragma unroll
+            for (int i = 0; i < NE; i++) {
+                const int64_t j = j0 + threadIdx.x + int64_t(i) * 256;
+                x[i] = 0;
+                pos[i] = 0;
+                unres[i] = 0;
+                hit[i] = 0;
+                if (j < je) {
+                    x[i] = t[j];
+                    pos[i] = base + pf[j];
+                    if (fl[j]) ownm |= 1u << i;
+                }
+            }
+            const int64_t x_lo = t[j0], x_hi = t[je - 1];
+
+            /* 1. rank over every other stream + older-stream hit masks */
+            for (int f2 = nsets - 1; f2 >= 0; f2--) {
+                if (f2 == f) continue;
+                const DevGroup g2 = a.m.groups[f2][s];
+                const int64_t *t2 = a.m.ts[f2] + g2.row_off;
+                const int32_t *pf2 = a.m.prefix[f2] + g2.row_off;
+                const uint8_t *fl2 = a.m.flags[f2] + g2.row_off;
+                const int64_t n2 = g2.nrows;
+                if (n2 == 0) continue;
+                if (threadIdx.x == 0) {
+                    int64_t lo = 0, hi = n2;
+                    while (lo < hi) {
+                        int64_t m = (lo + hi) >> 1;
+                        if (t2[m] < x_lo) lo = m + 1; else hi = m;
+                    }
+                    wb_sh[0] = lo;
+                    int64_t lo2 = lo, hi2 = n2;
+                    while (lo2 < hi2) {
+                        int64_t m = (lo2 + hi2) >> 1;
+                        if (t2[m] <= x_hi) lo2 = m + 1; else hi2 = m;
+                    }
+                    wb_sh[1] = lo2;
+                }
+                __syncthreads();
+                const int64_t wl = wb_sh[0], wend = wb_sh[1];
+                __syncthreads();
+                if (wl == wend) { /* tile range absent from t2: rank only */
+                    if (wl > 0) {
+                        const int64_t add = pf2[wl - 1] + fl2[wl - 1];
+#pragma unroll
+                        for (int i = 0; i < NE; i++)
+                            if (ownm >> i & 1) pos[i] += add;
+                    }
+                    continue;
+                }
+                uint32_t todo = ownm; /* non-owners need no rank */
+                for (int64_t wbase = wl; wbase < wend; wbase += CM_W) {
+                    const int wcnt = int(wend - wbase < CM_W ? wend - wbase
+                                                             : CM_W);
+                    for (int i = threadIdx.x; i < wcnt; i += blockDim.x) {
+                        wts[i] = t2[wbase + i];
+                        wpf[i] = pf2[wbase + i];
+                        wfl[i] = fl2[wbase + i];
+                    }
+                    __syncthreads();
+                    const int64_t w_last = wts[wcnt - 1];
+                    const bool last_chunk = wbase + wcnt == wend;
+#pragma unroll
+                    for (int i = 0; i < NE; i++) {
+                        if (!(todo >> i & 1) ||
+                            !(x[i] <= w_last || last_chunk))
+                            continue;
+                        todo &= ~(1u << i);
+                        int lo = 0, hi = wcnt; /* LDS lower bound */
+                        while (lo < hi) {
+                            int m = (lo + hi) >> 1;
+                            if (wts[m] < x[i]) lo = m + 1; else hi = m;
+                        }
+                        const int64_t p2 = wbase + lo;
+                        if (lo > 0)
+                            pos[i] += wpf[lo - 1] + wfl[lo - 1];
+                        else if (p2 > 0)
+                            pos[i] += pf2[p2 - 1] + fl2[p2 - 1];
+                        if (f2 < f && lo < wcnt && wts[lo] == x[i])
+                            hit[i] |= uint16_t(1u << f2);
+                    }
+                    __syncthreads();
+                }
+            }
+
+            /* 2. own row: ts + this stream's valid columns */
+#pragma unroll
+            for (int i = 0; i < NE; i++)
+                if (ownm >> i & 1) out_ts[pos[i]] = x[i];
+            for (int c = 0; c < ncols; c++) {
+                const void *src = a.val[f * ncols + c];
+                const uint8_t *vd = a.valid[f * ncols + c];
+                void *dst = a.out_val[c];
+                uint8_t *dvd = a.out_valid[c];
+                const bool wide = a.wide >> c & 1;
+#pragma unroll
+                for (int i = 0; i < NE; i++) {
+                    if (!(ownm >> i & 1)) continue;
+                    const int64_t row =
+                        g.row_off + j0 + threadIdx.x + int64_t(i) * 256;
+                    if (src && (!vd || vd[row])) {
+                        cm_move_cell(dst, pos[i], src, row, wide);
+                        if (dvd) dvd[pos[i]] = 1;
+                    } else {
+                        unres[i] |= 1u << c;
+                    }
+                }
+            }
+
+            /* 3. walk-back over older streams, newest first */
+            uint32_t need = 0; /* older streams some unresolved element hits */
+#pragma unroll
+            for (int i = 0; i < NE; i++)
+                if (unres[i]) need |= hit[i];
+            if (__syncthreads_or(need != 0)) {
+                for (int f2 = f - 1; f2 >= 0; f2--) {
+                    need = 0;
+#pragma unroll
+                    for (int i = 0; i < NE; i++)
+                        if (unres[i]) need |= hit[i];
+                    if (!__syncthreads_or(need >> f2 & 1)) continue;
+                    const DevGroup g2 = a.m.groups[f2][s];
+                    const int64_t *t2 = a.m.ts[f2] + g2.row_off;
+                    const int64_t n2 = g2.nrows;
+                    if (threadIdx.x == 0) {
+                        int64_t lo = 0, hi = n2;
+                        while (lo < hi) {
+                            int64_t m = (lo + hi) >> 1;
+                            if (t2[m] < x_lo) lo = m + 1; else hi = m;
+                        }
+                        wb_sh[0] = lo;
+                        int64_t lo2 = lo, hi2 = n2;
+                        while (lo2 < hi2) {
+                            int64_t m = (lo2 + hi2) >> 1;
+                            if (t2[m] <= x_hi) lo2 = m + 1; else hi2 = m;
+                        }
+                        wb_sh[1] = lo2;
+                    }
+                    __syncthreads();
+                    const int64_t wl = wb_sh[0], wend = wb_sh[1];
+                    __syncthreads();
+                    uint32_t todo = 0;
+#pragma unroll
+                    for (int i = 0; i < NE; i++)
+                        if (unres[i] && (hit[i] >> f2 & 1)) todo |= 1u << i;
+                    for (int64_t wbase = wl; wbase < wend; wbase += CM_W) {
+                        const int wcnt = int(wend - wbase < CM_W
+                                                 ? wend - wbase : CM_W);
+                        for (int i = threadIdx.x; i < wcnt; i += blockDim.x)
+                            wts[i] = t2[wbase + i];
+                        __syncthreads();
+                        const int64_t w_last = wts[wcnt - 1];
+                        const bool last_chunk = wbase + wcnt == wend;
+#pragma unroll
+                        for (int i = 0; i < NE; i++) {
+                            if (!(todo >> i & 1) ||
+                                !(x[i] <= w_last || last_chunk))
+                                continue;
+                            todo &= ~(1u << i);
+                            int lo = 0, hi = wcnt;
+                            while (lo < hi) {
+                                int m = (lo + hi) >> 1;
+                                if (wts[m] < x[i]) lo = m + 1; else hi = m;
+                            }
+                            if (lo >= wcnt || wts[lo] != x[i]) continue;
+                            const int64_t row2 = g2.row_off + wbase + lo;
+                            for (int c = 0; c < ncols; c++) {
+                                if (!(unres[i] >> c & 1)) continue;
+                                const void *src = a.val[f2 * ncols + c];
+                                const uint8_t *vd = a.valid[f2 * ncols + c];
+                                if (!src || (vd && !vd[row2])) continue;
+                                cm_move_cell(a.out_val[c], pos[i], src, row2,
+                                             a.wide >> c & 1);
+                                uint8_t *dvd = a.out_valid[c];
+                                if (dvd) dvd[pos[i]] = 1;
+                                unres[i] &= ~(1u << c);
+                            }
+                        }
+                        __syncthreads();
+                    }
+                }
+            }
+
+            /* 4. leftovers: null in every stream holding the timestamp */
+            for (int c = 0; c < ncols; c++) {
+                void *dst = a.out_val[c];
+                uint8_t *dvd = a.out_valid[c];
+                const bool wide = a.wide >> c & 1;
+#pragma unroll
+                for (int i = 0; i < NE; i++) {
+                    if (!(unres[i] >> c & 1)) continue;
+                    if (wide) ((uint64_t *)dst)[pos[i]] = 0;
+                    else ((uint8_t *)dst)[pos[i]] = 0;
+                    if (dvd) dvd[pos[i]] = 0;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 /* --------------------------------------------------- fused filtered scan
  * Fast path of gs_scan when every ts page is RLE (the TSBS shape), every
  * field page is all-valid Gorilla and no tombstones apply: the span of
@@ -5041,6 +5313,79 @@ GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
     return check_dev_err(ctx);
 }
 
+/* Host-side setup shared by both merge entries: everything that depends
+ * on the timestamps only.  Allocates the per-stream flag/prefix scratch,
+ * runs k_cm_flags + k_cm_prefix once, and turns the per-(stream, series)
+ * owner counts into per-series output offsets (host copy in ooff, device
+ * copy enqueued on the ctx stream).  The caller launches its scatter
+ * kernel, synchronizes, and frees plan.scratch. */
+namespace {
+struct CmPlan {
+    CompactArgs a;
+    std::vector<void *> scratch;
+    std::vector<int64_t> ooff; /* [nseries+1] */
+    int nseries = 0;
+    int gx = 0;
+    void release() {
+        for (void *p : scratch) hipFree(p);
+        scratch.clear();
+    }
+};
+
+GsStatus cm_plan_ranks(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
+                       const int64_t *const *d_ts, CmPlan &pl) {
+    const int nseries = pl.nseries;
+    CompactArgs &a = pl.a;
+    memset(&a, 0, sizeof(a));
+    for (int f = 0; f < nsets; f++) {
+        a.ts[f] = d_ts[f];
+        a.groups[f] = sets[f]->d_sgroups;
+        size_t rows = size_t(sets[f]->total_rows);
+        uint8_t *fl;
+        int32_t *pf;
+        if (hipMalloc(&fl, rows ? rows : 1) != hipSuccess)
+            return fail(GS_ERR, "hipMalloc compact scratch failed");
+        pl.scratch.push_back(fl);
+        if (hipMalloc(&pf, (rows ? rows : 1) * 4) != hipSuccess)
+            return fail(GS_ERR, "hipMalloc compact scratch failed");
+        pl.scratch.push_back(pf);
+        a.flags[f] = fl;
+        a.prefix[f] = pf;
+    }
+    int64_t *d_counts, *d_ooff;
+    if (hipMalloc(&d_counts, size_t(nsets) * nseries * 8) != hipSuccess)
+        return fail(GS_ERR, "hipMalloc compact tables failed");
+    pl.scratch.push_back(d_counts);
+    if (hipMalloc(&d_ooff, size_t(nseries) * 8) != hipSuccess)
+        return fail(GS_ERR, "hipMalloc compact tables failed");
+    pl.scratch.push_back(d_ooff);
+    a.counts = d_counts;
+    a.out_off = d_ooff;
+
+    pl.gx = nseries > 2048 ? 2048 : nseries;
+    hipLaunchKernelGGL(k_cm_flags, dim3(pl.gx, nsets), dim3(256), 0,
+                       ctx->stream, a, nsets, nseries, ctx->d_err);
+    int total = nsets * nseries;
+    hipLaunchKernelGGL(k_cm_prefix,
+                       dim3(total > 65535 ? 65535 : total), dim3(256), 0,
+                       ctx->stream, a, nsets, nseries);
+    std::vector<int64_t> counts(size_t(nsets) * nseries);
+    pl.ooff.assign(size_t(nseries) + 1, 0);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(counts.data(), d_counts, counts.size() * 8,
+                      hipMemcpyDeviceToHost));
+    int64_t acc = 0;
+    for (int s = 0; s < nseries; s++) {
+        pl.ooff[s] = acc;
+        for (int f = 0; f < nsets; f++) acc += counts[size_t(f) * nseries + s];
+    }
+    pl.ooff[nseries] = acc;
+    HIP_TRY(hipMemcpyAsync(d_ooff, pl.ooff.data(), size_t(nseries) * 8,
+                           hipMemcpyHostToDevice, ctx->stream));
+    return GS_OK;
+}
+} // namespace
+
 GsStatus gs_compact_merge(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
                           const int64_t *const *d_ts,
                           const double *const *d_val,
@@ -5056,68 +5401,115 @@ GsStatus gs_compact_merge(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
             return fail(GS_ERR, "all streams must cover the same series list");
     HIP_TRY(hipSetDevice(ctx->device));
 
-    CompactArgs a;
-    memset(&a, 0, sizeof(a));
-    std::vector<void *> scratch;
-    auto cleanup = [&]() { for (void *p : scratch) hipFree(p); };
+    CmPlan pl;
+    pl.nseries = nseries;
+    GsStatus st = cm_plan_ranks(ctx, sets, nsets, d_ts, pl);
+    if (st != GS_OK) { pl.release(); return st; }
     for (int f = 0; f < nsets; f++) {
-        a.ts[f] = d_ts[f];
-        a.val[f] = d_val[f];
-        a.valid[f] = d_valid ? d_valid[f] : nullptr;
-        a.groups[f] = sets[f]->d_sgroups;
-        size_t rows = size_t(sets[f]->total_rows);
-        uint8_t *fl;
-        int32_t *pf;
-        if (hipMalloc(&fl, rows ? rows : 1) != hipSuccess ||
-            hipMalloc(&pf, (rows ? rows : 1) * 4) != hipSuccess) {
-            cleanup();
-            return fail(GS_ERR, "hipMalloc compact scratch failed");
-        }
-        scratch.push_back(fl);
-        scratch.push_back(pf);
-        a.flags[f] = fl;
-        a.prefix[f] = pf;
+        pl.a.val[f] = d_val[f];
+        pl.a.valid[f] = d_valid ? d_valid[f] : nullptr;
     }
-    int64_t *d_counts, *d_ooff;
-    if (hipMalloc(&d_counts, size_t(nsets) * nseries * 8) != hipSuccess ||
-        hipMalloc(&d_ooff, size_t(nseries) * 8) != hipSuccess) {
-        cleanup();
-        return fail(GS_ERR, "hipMalloc compact tables failed");
-    }
-    scratch.push_back(d_counts);
-    scratch.push_back(d_ooff);
-    a.counts = d_counts;
-    a.out_off = d_ooff;
-
-    int gx = nseries > 2048 ? 2048 : nseries;
-    hipLaunchKernelGGL(k_cm_flags, dim3(gx, nsets), dim3(256), 0, ctx->stream,
-                       a, nsets, nseries, ctx->d_err);
-    int total = nsets * nseries;
-    hipLaunchKernelGGL(k_cm_prefix,
-                       dim3(total > 65535 ? 65535 : total), dim3(256), 0,
-                       ctx->stream, a, nsets, nseries);
-    std::vector<int64_t> counts(size_t(nsets) * nseries), ooff(nseries + 1);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(counts.data(), d_counts, counts.size() * 8,
-                      hipMemcpyDeviceToHost));
-    int64_t acc = 0;
-    for (int s = 0; s < nseries; s++) {
-        ooff[s] = acc;
-        for (int f = 0; f < nsets; f++) acc += counts[size_t(f) * nseries + s];
-    }
-    ooff[nseries] = acc;
-    HIP_TRY(hipMemcpyAsync(d_ooff, ooff.data(), size_t(nseries) * 8,
-                           hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_cm_scatter, dim3(gx, nsets), dim3(256), 0,
-                       ctx->stream, a, nsets, nseries, d_out_ts, d_out_val,
+    hipLaunchKernelGGL(k_cm_scatter, dim3(pl.gx, nsets), dim3(256), 0,
+                       ctx->stream, pl.a, nsets, nseries, d_out_ts, d_out_val,
                        d_out_valid);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    cleanup();
-    GsStatus st = check_dev_err(ctx);
+    hipError_t he = hipStreamSynchronize(ctx->stream);
+    pl.release();
+    HIP_TRY(he);
+    st = check_dev_err(ctx);
     if (st != GS_OK) return st;
     if (h_out_offsets)
-        memcpy(h_out_offsets, ooff.data(), size_t(nseries + 1) * 8);
-    if (out_rows) *out_rows = acc;
+        memcpy(h_out_offsets, pl.ooff.data(), size_t(nseries + 1) * 8);
+    if (out_rows) *out_rows = pl.ooff[nseries];
+    return GS_OK;
+}
+
+GsStatus gs_compact_merge_fields(GsCtx *ctx, GsGroupSet *const *sets,
+                                 int32_t nsets, int32_t ncols,
+                                 const int32_t *elem_size,
+                                 const int64_t *const *d_ts,
+                                 const void *const *d_val,
+                                 const uint8_t *const *d_valid,
+                                 int64_t *d_out_ts, void *const *d_out_val,
+                                 uint8_t *const *d_out_valid,
+                                 int64_t *h_out_offsets, int64_t *out_rows) {
+    if (!ctx || !sets || !elem_size || !d_ts || !d_val || !d_out_ts ||
+        !d_out_val)
+        return fail(GS_ERR, "bad args to gs_compact_merge_fields");
+    if (nsets < 1 || nsets > GS_MAX_STREAMS)
+        return fail(GS_ERR, "gs_compact_merge_fields: nsets outside "
+                            "1..GS_MAX_STREAMS");
+    if (ncols < 1 || ncols > GS_MAX_MERGE_COLS)
+        return fail(GS_ERR, "gs_compact_merge_fields: ncols outside "
+                            "1..GS_MAX_MERGE_COLS");
+    uint32_t wide = 0;
+    for (int c = 0; c < ncols; c++) {
+        if (elem_size[c] != 8 && elem_size[c] != 1)
+            return fail(GS_ERR, "gs_compact_merge_fields: elem_size must be "
+                                "8 or 1");
+        if (!d_out_val[c])
+            return fail(GS_ERR, "gs_compact_merge_fields: NULL output column");
+        if (elem_size[c] == 8) wide |= 1u << c;
+    }
+    for (int f = 0; f < nsets; f++)
+        if (!sets[f] || !d_ts[f])
+            return fail(GS_ERR, "gs_compact_merge_fields: NULL stream");
+    int nseries = sets[0]->nsgroups;
+    for (int f = 0; f < nsets; f++)
+        if (sets[f]->nsgroups != nseries)
+            return fail(GS_ERR, "all streams must cover the same series list");
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    CmPlan pl;
+    pl.nseries = nseries;
+    GsStatus st = cm_plan_ranks(ctx, sets, nsets, d_ts, pl);
+    /* an unsorted stream is known once the flags kernel has run */
+    if (st == GS_OK) st = check_dev_err(ctx);
+    if (st != GS_OK) {
+        hipStreamSynchronize(ctx->stream);
+        pl.release();
+        return st;
+    }
+
+    /* device pointer table: val | valid | out_val | out_valid */
+    const size_t ncell = size_t(nsets) * ncols;
+    std::vector<const void *> tab(2 * ncell + 2 * size_t(ncols), nullptr);
+    for (size_t i = 0; i < ncell; i++) {
+        tab[i] = d_val[i];
+        tab[ncell + i] = d_valid ? d_valid[i] : nullptr;
+    }
+    for (int c = 0; c < ncols; c++) {
+        tab[2 * ncell + c] = d_out_val[c];
+        tab[2 * ncell + ncols + c] = d_out_valid ? d_out_valid[c] : nullptr;
+    }
+    const void **d_tab;
+    if (hipMalloc(&d_tab, tab.size() * sizeof(void *)) != hipSuccess) {
+        hipStreamSynchronize(ctx->stream);
+        pl.release();
+        return fail(GS_ERR, "hipMalloc compact pointer table failed");
+    }
+    pl.scratch.push_back(d_tab);
+    hipError_t he = hipMemcpyAsync(d_tab, tab.data(),
+                                   tab.size() * sizeof(void *),
+                                   hipMemcpyHostToDevice, ctx->stream);
+    if (he == hipSuccess) {
+        CompactFieldsArgs fa;
+        fa.m = pl.a;
+        fa.val = d_tab;
+        fa.valid = (const uint8_t *const *)(d_tab + ncell);
+        fa.out_val = (void *const *)(d_tab + 2 * ncell);
+        fa.out_valid = (uint8_t *const *)(d_tab + 2 * ncell + ncols);
+        fa.wide = wide;
+        fa.ncols = ncols;
+        hipLaunchKernelGGL(k_cm_scatter_fields, dim3(pl.gx, nsets), dim3(256),
+                           0, ctx->stream, fa, nsets, nseries, d_out_ts);
+    }
+    hipError_t hs = hipStreamSynchronize(ctx->stream);
+    pl.release();
+    HIP_TRY(he);
+    HIP_TRY(hs);
+    if (h_out_offsets)
+        memcpy(h_out_offsets, pl.ooff.data(), size_t(nseries + 1) * 8);
+    if (out_rows) *out_rows = pl.ooff[nseries];
     return GS_OK;
 }
 

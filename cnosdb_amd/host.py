@@ -181,6 +181,14 @@ class PageLib:
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
             ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p,
             ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+        lib.gs_compact_merge_fields.restype = ctypes.c_int32
+        lib.gs_compact_merge_fields.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+            ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+            ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
 
     def err(self):
         return self.lib.gs_last_error().decode()
@@ -522,6 +530,52 @@ class Engine:
             _np_ptr(offs), ctypes.byref(rows))
         if st != 0:
             raise RuntimeError(f"gs_compact_merge failed ({st}): {self._pl.err()}")
+        return rows.value, offs
+
+    def compact_merge_fields(self, gsets, d_ts_list, cols, d_out_ts,
+                             d_out_cols):
+        """k-way merge+dedup over every field column of a column group
+        (take_last_and_merge, batch_builder.rs:132-155): per column the
+        newest non-null value wins.  gsets oldest->newest; cols[f][c] =
+        (values_tensor_or_None, valid_tensor_or_None), a None values
+        tensor meaning column c is absent from stream f; d_out_cols[c] =
+        (values_tensor, valid_tensor_or_None).  Element sizes come from
+        the output tensors' dtypes (float64/int64 -> 8, uint8 -> 1; u64
+        travels as int64 bits).  Returns (out_rows, per-series offsets
+        np.array)."""
+        k = len(gsets)
+        ncols = len(d_out_cols)
+        for f in range(k):
+            if len(cols[f]) != ncols:
+                raise ValueError(f"stream {f}: {len(cols[f])} columns, "
+                                 f"outputs have {ncols}")
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        sets = (ctypes.c_void_p * k)(*[g._h for g in gsets])
+        ts_p = (ctypes.c_void_p * k)(*[t.data_ptr() for t in d_ts_list])
+        val_p = (ctypes.c_void_p * (k * ncols))(
+            *[ptr(cols[f][c][0]) for f in range(k) for c in range(ncols)])
+        vds = [cols[f][c][1] for f in range(k) for c in range(ncols)]
+        vd_p = None  # whole array NULL: every present column all-valid
+        if any(v is not None for v in vds):
+            vd_p = (ctypes.c_void_p * (k * ncols))(*[ptr(v) for v in vds])
+        esz = (ctypes.c_int32 * ncols)(
+            *[v.element_size() for v, _ in d_out_cols])
+        oval_p = (ctypes.c_void_p * ncols)(
+            *[v.data_ptr() for v, _ in d_out_cols])
+        ovd_p = (ctypes.c_void_p * ncols)(*[ptr(v) for _, v in d_out_cols])
+        nseries = self.lib.gs_set_series(gsets[0]._h)
+        offs = np.zeros(nseries + 1, dtype=np.int64)
+        rows = ctypes.c_int64(0)
+        st = self.lib.gs_compact_merge_fields(
+            self._ctx, sets, k, ncols, esz, ts_p, val_p, vd_p,
+            ctypes.c_void_p(d_out_ts.data_ptr()), oval_p, ovd_p,
+            _np_ptr(offs), ctypes.byref(rows))
+        if st != 0:
+            raise RuntimeError(
+                f"gs_compact_merge_fields failed ({st}): {self._pl.err()}")
         return rows.value, offs
 
     def encode_pages_dev(self, kind, d_vals, row_off, rows, d_out,

@@ -328,6 +328,54 @@ GsStatus gs_compact_merge(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
                           double *d_out_val, uint8_t *d_out_valid,
                           int64_t *h_out_offsets, int64_t *out_rows);
 
+/* ---- compaction merge over every field column of a column group ----
+ * The reference never compacts one column at a time: a column group is a
+ * time column plus all of the table's field columns, and
+ * BatchMergeBuilder::take_last_and_merge (tskv/src/reader/
+ * batch_builder.rs:132-155) resolves each column independently over the
+ * rows that share a timestamp.  Streams, series lists, the merged
+ * timestamp stream (sorted union per series), h_out_offsets and out_rows
+ * are exactly those of gs_compact_merge; raw sets (gs_raw_set) are
+ * accepted like any other set.  The ownership/rank work depends on the
+ * timestamps only and runs once for any ncols.
+ *
+ * Per cell (timestamp, column c): the value comes from the NEWEST stream
+ * that contains the timestamp, has column c present and is valid there —
+ * a newer null never hides an older valid value.  With no such stream the
+ * value slot is all-zero bytes and the validity byte 0.
+ *
+ * d_val / d_valid are [nsets*ncols] tables indexed f*ncols + c.  A NULL
+ * d_val entry means column c is absent from stream f (an older file after
+ * ALTER TABLE ADD FIELD has no page for it) and behaves exactly like an
+ * all-null column; a NULL d_valid entry (or a NULL d_valid array) means
+ * all rows valid.  d_out_val[c] (required) and d_out_valid[c] (entries or
+ * the array may be NULL) are caller device buffers sized >= the sum of
+ * input rows.
+ *
+ * Values move as raw bits, elem_size[c] bytes each: 8 for f64/i64/u64, 1
+ * for bool — the widths gs_decode writes.  No arithmetic touches a value:
+ * NaN payloads, i64 beyond 2^53 and u64 beyond 2^63 come out unchanged.
+ *
+ * GS_ERR (with a message, before any device work) for ncols outside
+ * 1..GS_MAX_MERGE_COLS, an elem_size outside {1, 8}, nsets outside
+ * 1..GS_MAX_STREAMS, a NULL required pointer, or mismatched series
+ * counts.  An unsorted stream fails as in gs_compact_merge. */
+#define GS_MAX_STREAMS 16
+#define GS_MAX_MERGE_COLS 32
+
+GsStatus gs_compact_merge_fields(
+    GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
+    int32_t ncols, const int32_t *elem_size,   /* [ncols], each 8 or 1 */
+    const int64_t *const *d_ts,                /* [nsets] */
+    const void *const *d_val,                  /* [nsets*ncols], index f*ncols+c;
+                                                  NULL entry = column c absent in stream f */
+    const uint8_t *const *d_valid,             /* same indexing; NULL entry = all rows valid;
+                                                  the array itself may be NULL */
+    int64_t *d_out_ts,
+    void *const *d_out_val,                    /* [ncols] */
+    uint8_t *const *d_out_valid,               /* [ncols]; entries or the array may be NULL */
+    int64_t *h_out_offsets, int64_t *out_rows);
+
 /* ---- Arrow C Data Interface export (decode output as
  * ArrowArray so the Rust shim reconstitutes RecordBatches zero-copy from
  * the shim's side).  GsArrowArray is layout-identical to `struct
