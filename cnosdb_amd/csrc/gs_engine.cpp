@@ -2887,6 +2887,14 @@ struct GorAggArgs {
  * (n_buckets > 8192 at that shape), so that range keeps the old path. */
 #define GS_AGG_FUSED_MIN_ROWS 2
 
+/* k_gor_chunks_filtered: window bit count of a parked lane (never drops
+ * below 64, so a parked lane never refills), and what a lane's stop row S
+ * stands for */
+#define GOR_PARK_NB (1 << 30)
+#define GOR_FK_END 0   /* the chunk's own end: check the bit count */
+#define GOR_FK_CLEAN 1 /* span end inside a GORF_SAFE_STOP chunk: no check */
+#define GOR_FK_OVER 2  /* the refill overran the stream: always an error */
+
 template <bool AGG>
 __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
                                       const DevGorChunk *__restrict__ chunks,
@@ -2899,9 +2907,11 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
                                       unsigned *__restrict__ err,
                                       GorAggArgs ag) {
     __shared__ double ring[GS_GOR_BLOCK / 64][GS_RING][64 + 1];
-    /* per-flush lane descriptors: {dst pointer, staged count} packed so the
-       flush loop reads ONE broadcast ds_read per source lane instead of
-       three cross-lane shuffles */
+    /* per-flush lane descriptors: {element offset into out, staged count}
+       packed so the flush loop reads ONE broadcast ds_read per source lane
+       instead of three cross-lane shuffles.  An offset, not a pointer: a
+       pointer that travels through LDS loses its address space and the
+       stores become flat (counted against lgkmcnt as well as vmcnt). */
     __shared__ uint64_t fdesc[GS_GOR_BLOCK / 64][64][2];
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
@@ -2922,17 +2932,70 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
         int32_t sel_lo = int32_t(sp_start[ch.grp]);
         int32_t sel_hi = int32_t(sel_lo + sp_cnt[ch.grp]);
         if (!have) { sel_lo = 0; sel_hi = 0; }
-        double *o = out + out_off[ch.grp] - sel_lo; /* o[r] valid in span */
         int32_t r = int32_t(ch.row0);
-        int32_t end = r + int32_t(ch.cnt);
+        const int32_t end = r + int32_t(ch.cnt);
+        /* rows [sel_lo, stage_hi) of this chunk are staged; the staged run
+           is contiguous, so the output cursor only ever advances by the
+           count of each flush */
+        const int32_t stage_hi = sel_hi < end ? sel_hi : end;
+        const uint32_t span_w =
+            stage_hi > sel_lo ? uint32_t(stage_hi - sel_lo) : 0u;
+        uint64_t o_cur = uint64_t(out_off[ch.grp]) +
+                         uint64_t((r > sel_lo ? r : sel_lo) - sel_lo);
         GorChunkState st = gor_chunk_init(blob, ch);
-        int rfill = 0;
-        int32_t run0 = 0; /* output row of first staged entry */
-        bool done = !have, over = false, clean_stop = false;
-        if (have && st.bad) { atomicOr(err, DERR_SHORT); done = true; }
+        bool live = have && ch.cnt > 0;
+        if (live && st.bad) { atomicOr(err, DERR_SHORT); live = false; }
+        /* Refill state.  The 128-bit window hi:lo holds nb valid bits;
+           nextw is the next big-endian word, raw2 the one after it exactly
+           as loaded (swapped only when it is promoted to nextw, so nothing
+           touches the loaded register before the following refill and the
+           load latency hides behind a whole refill interval).  pl is the
+           address of the next load and stops at the last loadable word;
+           wrem counts the words left before the zero clamp, standing in
+           for GorChunkState's p: wrem > 0 <=> p < p_clamp, and
+           wrem <= -3 <=> a refill has found p >= p_over. */
+        uint64_t hi = 0, lo = 0, nextw = 0, raw2 = 0, val = 0;
+        int nb = GOR_PARK_NB;
+        uint32_t trailing = 0, meaningful = 64;
+        const uint8_t *pl = blob;
+        int32_t wrem = 0;
+        /* One stop row per chunk instead of per-row end tests: a chunk
+           that is not its page's last stops at its own end (fk END, the
+           bit count is checked there), a chunk the pre-pass proved
+           decodable at the span end if that comes first (fk CLEAN, no
+           check).  A last chunk without either parses on to the sentinel. */
+        int32_t S = INT32_MAX;
+        int fk = GOR_FK_END;
+        if (live) {
+            hi = st.hi; lo = st.lo; nb = st.nb;
+            nextw = st.nextw;
+            raw2 = __builtin_bswap64(st.nextw2);
+            val = st.val;
+            trailing = st.trailing;
+            meaningful = st.meaningful;
+            wrem = int32_t((st.p_clamp - st.p) >> 3);
+            pl = st.p;
+            if (ch.row0 == 0) {
+                /* the page's first value comes from the header: one zero
+                   control bit in front of the stream makes the first
+                   iteration parse it as a repeat of val, so the header
+                   row takes the same path as every other row (once it is
+                   consumed the bit accounting is that of the real stream) */
+                nb = 1;
+            }
+            if (!ch.last) S = end;
+            if ((ch.flags & GORF_SAFE_STOP) && sel_hi < S) {
+                S = sel_hi;
+                fk = GOR_FK_CLEAN;
+            }
+        } else {
+            r = INT32_MIN; /* parked from the start */
+        }
         /* AGG: current piece = rows [a_start, r) of bucket a_b; a_next is
            the page-local row at which bucket a_b+1 starts, a_slack how far
-           (ns) that row lies past the boundary itself */
+           (ns) that row lies past the boundary itself.  a_next is held at
+           INT32_MAX once it reaches stage_hi: a boundary row that is never
+           staged never closes a piece. */
         int32_t a_b = -1, a_next = INT32_MAX, a_start = 0;
         double a_mx = -__builtin_inf(), a_sm = 0.0;
         uint64_t a_slack = 0, a_rem = 0, a_d = 0;
@@ -2941,7 +3004,8 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
         bool a_head = false; /* the chunk's head slot has been written */
         if (AGG && have) {
             const int64_t d = ag.g_delta[ch.grp];
-            const int32_t rs = r > sel_lo ? r : sel_lo; /* first staged row */
+            const int32_t r0 = int32_t(ch.row0);
+            const int32_t rs = r0 > sel_lo ? r0 : sel_lo; /* first staged row */
             a_start = rs;
             a_cell0 = size_t(ag.grp_sg[ch.grp]) * size_t(ag.nbuckets);
             /* ts of row rs relative to the grid origin */
@@ -2955,7 +3019,7 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
                 const __int128 bound = (__int128)(a_b + 1) * ag.bucket_ns - x;
                 const __int128 k = (bound + d - 1) / d; /* rows, >= 1 */
                 a_slack = uint64_t(k * d - bound);
-                a_next = rs + k > INT32_MAX ? INT32_MAX : int32_t(rs + k);
+                a_next = rs + k >= stage_hi ? INT32_MAX : int32_t(rs + k);
                 const uint64_t q = uint64_t(ag.bucket_ns) / uint64_t(d);
                 a_q = q > INT32_MAX ? uint32_t(INT32_MAX) : uint32_t(q);
                 a_rem = uint64_t(ag.bucket_ns) % uint64_t(d);
@@ -2972,9 +3036,10 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
             m.cnt = cnt;
             ag.pc_meta[pi] = m;
         };
-        /* row r opens the next bucket: the piece that ends here is not the
-           chunk's last, so it is the head or complete.  Loops only when a
-           bucket is shorter than the row spacing (empty complete cells). */
+        /* row r (< stage_hi, so it will be staged) opens the next bucket:
+           the piece that ends here is not the chunk's last, so it is the
+           head or complete.  Loops only when a bucket is shorter than the
+           row spacing (empty complete cells). */
         auto agg_boundary = [&]() {
             do {
                 const int32_t cnt = r - a_start;
@@ -2998,27 +3063,45 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
                     int64_t nn = int64_t(a_next) + int64_t(a_q);
                     if (a_slack < a_rem) { a_slack += a_d; nn++; }
                     a_slack -= a_rem;
-                    a_next = nn > INT32_MAX ? INT32_MAX : int32_t(nn);
+                    a_next = nn >= stage_hi ? INT32_MAX : int32_t(nn);
                 }
             } while (a_next == r);
         };
+        /* the chunk's open piece at its stop row rr is its last: its only
+           one (head, no tail) or its tail.  Every active chunk writes both
+           slots. */
+        auto agg_tail = [&](int32_t rr) {
+            const int32_t e = rr < stage_hi ? rr : stage_hi;
+            const int32_t cnt = e > a_start ? e - a_start : 0;
+            const size_t pi = 2 * size_t(ch.slot);
+            if (!a_head) {
+                agg_put(pi, cnt);
+                DevAggMeta none;
+                none.bucket = AGG_NO_PIECE;
+                none.cnt = 0;
+                ag.pc_meta[pi + 1] = none;
+            } else {
+                agg_put(pi + 1, cnt);
+            }
+        };
+        if (AGG && have && !live) agg_tail(int32_t(ch.row0));
         auto topup = [&]() { /* only with nb < 64 */
-            uint64_t x = st.nextw;
-            st.nextw = st.nextw2;
-            over |= (st.p >= st.p_over);
-            st.nextw2 = (st.p < st.p_clamp) ? dev_be64(st.p) : 0;
-            st.p += 8;
-            if (st.nb == 0) { st.hi = x; st.lo = 0; }
-            else { st.hi |= x >> st.nb; st.lo = x << (64 - st.nb); }
-            st.nb += 64;
+            const uint64_t x = nextw;
+            nextw = wrem >= 0 ? __builtin_bswap64(raw2) : 0;
+            __builtin_memcpy(&raw2, pl, 8);
+            pl += wrem > 1 ? 8 : 0;
+            wrem--;
+            /* the bits of hi below nb are zero, so nb == 0 needs no case
+               of its own; (x << 1) << (63 - nb) is x << (64 - nb) without
+               the undefined shift by 64 */
+            hi |= x >> nb;
+            lo = (x << 1) << (63 - nb);
+            nb += 64;
         };
         auto consume = [&](unsigned k) { /* k in 1..=64 */
-            st.hi = (k == 64) ? st.lo : ((st.hi << k) | (st.lo >> (64 - k)));
-            st.lo = (k == 64) ? 0 : (st.lo << k);
-            st.nb -= int(k);
-        };
-        auto used_bits = [&]() {
-            return int64_t(st.p - st.stream) * 8 - 128 - st.nb;
+            hi = (k == 64) ? lo : ((hi << k) | (lo >> (64 - k)));
+            lo = (k == 64) ? 0 : (lo << k);
+            nb -= int(k);
         };
         auto fd = fdesc[wv];
         /* 4 source lanes per store instruction: lane = (sq:2, idx:4), sq
@@ -3029,10 +3112,14 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
            stores, the earlier register-batching lesson) */
         const int f_idx = lane & (GS_RING - 1);
         const int f_sq = lane / GS_RING;
-        double *rcur = &rslot[0][lane]; /* strength-reduced ring cursor */
+        double *const rbase = &rslot[0][lane];
+        double *rcur = rbase; /* strength-reduced ring cursor */
         auto flush = [&]() {
-            fd[lane][0] = (uint64_t)(uintptr_t)(o + int64_t(run0));
+            const int rfill = int(rcur - rbase) / 65;
+            fd[lane][0] = o_cur;
             fd[lane][1] = uint64_t(rfill);
+            o_cur += uint64_t(rfill);
+            rcur = rbase;
             __builtin_amdgcn_wave_barrier();
             constexpr int SRCP = 64 / GS_RING; /* sources per store */
             for (int src0 = 0; src0 < 64; src0 += SRCP * 4) {
@@ -3046,46 +3133,48 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
                     cnt[t] = int(fd[src][1]);
                 }
                 for (int t = 0; t < 4; t++)
-                    if (f_idx < cnt[t])
-                        ((double *)(uintptr_t)ob[t])[f_idx] = vbuf[t];
+                    if (f_idx < cnt[t]) out[ob[t] + uint64_t(f_idx)] = vbuf[t];
             }
-            rfill = 0;
-            rcur = &rslot[0][lane];
+            __builtin_amdgcn_wave_barrier();
         };
-        auto stage_row = [&](uint64_t bits_) {
-            if (r >= sel_lo && r < sel_hi) {
-                if (AGG) {
-                    if (r == a_next) agg_boundary();
-                    const double x = __longlong_as_double((long long)bits_);
-                    if (x > a_mx) a_mx = x;
-                    a_sm += x;
-                }
-                if (rfill == 0) run0 = r;
-                *rcur = __longlong_as_double((long long)bits_);
-                rcur += 65;
-                rfill++;
-            }
-            r++;
-            /* all rows produced (non-last chunk), or span passed on a
-               chunk the pre-pass proved decodable: stop parsing */
-            if (r == end && !ch.last) {
-                done = true;
-                if (used_bits() > st.total_bits) atomicOr(err, DERR_SHORT);
-            } else if (r >= sel_hi && (ch.flags & GORF_SAFE_STOP)) {
-                done = true;
-                clean_stop = true;
-            }
+        /* The lane's parse is over (sent: on the sentinel, whose iteration
+           staged nothing but did count a row; else at the stop row S).
+           Settle the error status and the last aggregate piece here, once,
+           then park: on an all-zero window every further iteration parses
+           a repeat, never refills, and r < 0 lies outside every span, so a
+           parked lane needs no guard in the loop. */
+        auto finish = [&](bool sent) {
+            const int32_t rr = sent ? r - 1 : r;
+            /* bits consumed so far: words fetched minus the two staged
+               ahead, minus what the window still holds */
+            const int64_t total = (int64_t(ch.data_len) - 10) * 8;
+            const int64_t W3 = int64_t((uint64_t(total) + 63) >> 6) + 3;
+            const int64_t used = (W3 - wrem) * 64 - 128 - nb;
+            bool bad;
+            if (fk == GOR_FK_OVER) bad = true;
+            else if (sent) bad = used > total || rr < end;
+            else bad = fk == GOR_FK_END && used > total;
+            if (bad) atomicOr(err, DERR_SHORT);
+            if (AGG) agg_tail(rr);
+            r = INT32_MIN;
+            hi = 0;
+            lo = 0;
+            nb = GOR_PARK_NB;
+            S = INT32_MAX;
+            a_next = INT32_MAX;
         };
-        if (!done && ch.row0 == 0 && r < end) stage_row(st.val);
-        unsigned it = 1; /* header stage counts toward the first cadence */
-        while (!__all(done)) {
-            if (!done) {
-                if (st.nb < 64) topup();
-                if (over) { atomicOr(err, DERR_SHORT); done = true; }
-            }
-            if (!done) {
-                uint32_t top13 = uint32_t(st.hi >> 51);
-                bool stg = true;
+        int32_t r_evt = S < a_next ? S : a_next; /* next row with an event */
+        /* GS_RING iterations stage at most GS_RING rows per lane, so one
+           flush per block can never overflow the ring — no ballot, and
+           the all-parked test runs once per block, not once per value */
+        bool more = !__all(r < 0);
+        while (more) {
+            /* not unrolled: bodies unrolled 2, 4 and 16 times measured the
+               same step time, so the smallest code is kept */
+#pragma unroll 1
+            for (int it = 0; it < GS_RING; it++) {
+                if (nb < 64) topup();
+                uint32_t top13 = uint32_t(hi >> 51);
                 {
                     /* uniform path (no repeat/xor branch): a repeat is an
                        XOR value with 0 meaningful bits (sb=0), so every
@@ -3100,57 +3189,63 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
                     uint32_t mg_raw = top13 & 0x3f;
                     uint32_t mg_new = mg_raw ? mg_raw : 64;
                     uint32_t tr_new = mg_raw ? (64 - lead - mg_raw) : 0;
-                    st.meaningful = nw ? mg_new : st.meaningful;
-                    st.trailing = nw ? tr_new : st.trailing;
+                    meaningful = nw ? mg_new : meaningful;
+                    trailing = nw ? tr_new : trailing;
                     unsigned shift = bit0 ? (bit1 ? 13u : 2u) : 1u;
-                    unsigned m_eff = bit0 ? st.meaningful : 0u;
+                    unsigned m_eff = bit0 ? meaningful : 0u;
                     unsigned need = shift + m_eff;
                     uint64_t sb;
                     if (__builtin_expect(need < 64, 1)) {
                         /* nb >= 64 after the loop-top topup; need < 64
                            keeps the consume branch-free (no k==64 case) */
-                        uint64_t w =
-                            (st.hi << shift) | (st.lo >> (64 - shift));
-                        sb = m_eff ? (w >> ((64 - m_eff) & 63)) : 0;
-                        st.hi = (st.hi << need) | (st.lo >> (64 - need));
-                        st.lo <<= need;
-                        st.nb -= int(need);
+                        uint64_t w = (hi << shift) | (lo >> (64 - shift));
+                        /* m_eff != 0 <=> bit0: a mask, not a branch */
+                        sb = (w >> ((64 - m_eff) & 63)) &
+                             (uint64_t(0) - uint64_t(bit0));
+                        hi = (hi << need) | (lo >> (64 - need));
+                        lo <<= need;
+                        nb -= int(need);
                     } else { /* m_eff >= 51: rare */
                         consume(shift);
-                        while (st.nb < int(m_eff)) topup();
-                        sb = (m_eff == 64) ? st.hi
-                                           : (st.hi >> (64 - m_eff));
+                        while (nb < int(m_eff)) topup();
+                        sb = (m_eff == 64) ? hi : (hi >> (64 - m_eff));
                         consume(m_eff);
                     }
-                    st.val ^= sb << st.trailing;
-                    if (bit0 && st.val == GORILLA_SENTINEL) {
-                        done = true;
-                        stg = false;
-                        if (used_bits() > st.total_bits)
-                            atomicOr(err, DERR_SHORT);
+                    val ^= sb << trailing;
+                    const bool sent = bit0 && val == GORILLA_SENTINEL;
+                    /* one exec region: both tests evaluated, no && */
+                    if (int(!sent) &
+                        int(uint32_t(r) - uint32_t(sel_lo) < span_w)) {
+                        const double x = __longlong_as_double((long long)val);
+                        if (AGG) {
+                            if (x > a_mx) a_mx = x;
+                            a_sm += x;
+                        }
+                        *rcur = x;
+                        rcur += 65;
+                    }
+                    r++;
+                    /* rare: the stop row, the sentinel, or (AGG) the row
+                       that opens the next bucket — closed before that row
+                       is staged, which is the next thing to happen */
+                    if (__builtin_expect(sent || r == r_evt, 0)) {
+                        if (sent || r == S) finish(sent);
+                        else if (AGG) agg_boundary();
+                        r_evt = S < a_next ? S : a_next;
                     }
                 }
-                if (stg && r < end) stage_row(st.val);
             }
-            if ((++it & (GS_RING - 1)) == 0) flush();
-        }
-        flush();
-        if (have && r < end && !clean_stop) atomicOr(err, DERR_SHORT);
-        if (AGG && have) {
-            /* the open piece is the chunk's last: its only one (head, no
-               tail) or its tail.  Every active chunk writes both slots. */
-            const int32_t e = r < sel_hi ? r : sel_hi;
-            const int32_t cnt = e > a_start ? e - a_start : 0;
-            const size_t pi = 2 * size_t(ch.slot);
-            if (!a_head) {
-                agg_put(pi, cnt);
-                DevAggMeta none;
-                none.bucket = AGG_NO_PIECE;
-                none.cnt = 0;
-                ag.pc_meta[pi + 1] = none;
-            } else {
-                agg_put(pi + 1, cnt);
+            flush();
+            /* overrun (a refill met p_over): reads past the clamp gave
+               zeros, i.e. repeats, so nothing was harmed in between; make
+               the next row this lane's stop.  Whatever else ends such a
+               lane first finds used > total and reports the same error. */
+            if (r >= 0 && wrem <= -3) {
+                fk = GOR_FK_OVER;
+                S = r + 1;
+                r_evt = S;
             }
+            more = !__all(r < 0);
         }
     }
 }
@@ -4766,9 +4861,6 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
     if (spec->n_buckets > 0) {
         if (!spec->d_agg_max || !spec->d_agg_sum || !spec->d_agg_count)
             return fail(GS_ERR, "agg outputs missing");
-        hipLaunchKernelGGL(k_build_sgroups_out, dim3(grid_for(nsg, 256)),
-                           dim3(256), 0, ctx->stream, set->d_sgroup_first,
-                           nsg, set->d_out_off, set->d_sgroups_out);
         size_t cells = size_t(nsg) * size_t(spec->n_buckets);
         if (set->partials_cap < cells) {
             if (set->d_pmax) hipFree(set->d_pmax);
@@ -4781,6 +4873,17 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
             set->partials_cap = cells;
         }
     }
+    /* d_sgroups_out is read by the separate aggregate kernels only: built
+       when the first field takes one of those branches, never on the
+       fused path */
+    bool sgroups_built = false;
+    auto build_sgroups = [&]() {
+        if (sgroups_built) return;
+        hipLaunchKernelGGL(k_build_sgroups_out, dim3(grid_for(nsg, 256)),
+                           dim3(256), 0, ctx->stream, set->d_sgroup_first,
+                           nsg, set->d_out_off, set->d_sgroups_out);
+        sgroups_built = true;
+    };
     for (int f = 0; f < nf; f++) {
         SlotPages &fsp = set->slots[1 + fields[f]];
         int nch = fsp.n_gor_chunks;
@@ -4884,6 +4987,7 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                     long v = e ? atol(e) : 0;
                     return int(v == 128 || v == 512 ? v : 256);
                 }();
+                build_sgroups();
                 hipLaunchKernelGGL(k_agg_partial_rle,
                                    dim3(nsg > 65535 ? 65535 : nsg),
                                    dim3(agg_block), shm_rle, ctx->stream,
@@ -4897,6 +5001,7 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                 size_t agg_shm = spec->n_buckets <= 8192
                                      ? (size_t(spec->n_buckets) + 1) * 4
                                      : 0;
+                build_sgroups();
                 hipLaunchKernelGGL(
                     k_agg_partial, dim3(nsg > 65535 ? 65535 : nsg),
                     dim3(256), agg_shm, ctx->stream, set->d_sgroups_out,
