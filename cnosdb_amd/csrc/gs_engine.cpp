@@ -2758,45 +2758,80 @@ __global__ void k_spans_rle(const uint8_t *__restrict__ blob,
     }
 }
 
-/* RLE ts generation of only the selected span, compacted */
-__global__ void k_rle_ts_filtered(const uint8_t *__restrict__ blob,
-                                  const DevPage *__restrict__ pages,
-                                  int npages,
-                                  const int64_t *__restrict__ sp_start,
-                                  const int64_t *__restrict__ sp_cnt,
-                                  const int64_t *__restrict__ out_off,
-                                  int64_t *__restrict__ out_ts) {
-    for (int p = blockIdx.x; p < npages; p += gridDim.x) {
-        DevPage pg = pages[p];
-        const uint8_t *s = blob + pg.data_off + 1;
-        uint64_t scaler = 1;
-        unsigned s10 = s[0] & 0x0f;
-        for (unsigned k = 0; k < s10; k++) scaler *= 10;
-        const uint8_t *q = s + 1;
-        int64_t first = int64_t(dev_be64(q));
-        uint64_t dv; uint32_t nr;
-        dev_varint(q + 8, pg.data_len - 10, &dv, &nr);
-        int64_t delta = int64_t(dv * scaler);
-        int64_t st = sp_start[pg.grp], cnt = sp_cnt[pg.grp];
-        int64_t *o = out_ts + out_off[pg.grp];
-        /* paired 16-B stores: closed-form generation is pure store
-           bandwidth; halving the store-instruction count lifted the
-           measured rate (the 1-row peel goes by the destination address,
-           so a caller's 8-B-aligned buffer is as good as a 16-B one) */
-        const uint64_t base = uint64_t(first) + uint64_t(st) * uint64_t(delta);
-        const int64_t head = int64_t((uintptr_t(o) >> 3) & 1);
-        if (head && threadIdx.x == 0 && cnt > 0) o[0] = int64_t(base);
-        const int64_t n2 = (cnt - head) >> 1;
-        longlong2 *op = (longlong2 *)(o + head);
-        for (int64_t q2 = threadIdx.x; q2 < n2; q2 += blockDim.x) {
-            const uint64_t r0 = uint64_t(head) + 2 * uint64_t(q2);
-            longlong2 v;
-            v.x = int64_t(base + r0 * uint64_t(delta));
-            v.y = int64_t(base + (r0 + 1) * uint64_t(delta));
-            op[q2] = v;
+#define GS_TS_TILE 16384 /* output rows per work item of k_rle_ts_tiles */
+
+/* First non-empty page-group at or after g0 whose compacted rows reach past
+ * output row r: the smallest g in [g0, ngroups) with out_off[g + 1] > r.
+ * The caller guarantees r < out_off[ngroups].  Uniform over the block (the
+ * loads are scalar); out_off is small enough to stay in L2. */
+__device__ __forceinline__ int ts_group_of(const int64_t *__restrict__ out_off,
+                                           int g0, int ngroups, int64_t r) {
+    int lo = g0, hi = ngroups - 1;
+    while (lo < hi) {
+        int mid = lo + ((hi - lo) >> 1);
+        if (out_off[mid + 1] > r) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+/* RLE ts generation of only the selected spans, compacted.  The work item
+ * is a tile of `tile` OUTPUT rows, not a page: every block stores the same
+ * number of bytes whatever the page size, the pages per series or the
+ * selection (one block per page left half the chip idle whenever the page
+ * index modulo the grid lined up with the selected pages).  Row j of group
+ * g is g_t0sel[g] + j * g_delta[g] (k_spans_rle), so no page header is
+ * read here.  A tile finds its first group by binary search in out_off and
+ * walks forward; runs of empty groups are skipped by another search.
+ * Writes exactly rows [out_off[0], out_off[ngroups]). */
+__global__ __launch_bounds__(256) void k_rle_ts_tiles(
+    const int64_t *__restrict__ out_off, int ngroups,
+    const int64_t *__restrict__ g_t0sel, const int64_t *__restrict__ g_delta,
+    int tile, int64_t *__restrict__ out_ts) {
+    const int64_t first = out_off[0];
+    const int64_t total = out_off[ngroups];
+    const int64_t ntiles = (total - first + tile - 1) / tile;
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        int64_t r = first + t * tile;
+        const int64_t r_end = r + tile < total ? r + tile : total;
+        int g = ts_group_of(out_off, 0, ngroups, r);
+        while (true) {
+            /* rows [r, seg_end) of group g, which holds row r */
+            const int64_t g_first = out_off[g], g_end = out_off[g + 1];
+            const int64_t seg_end = g_end < r_end ? g_end : r_end;
+            const int64_t cnt = seg_end - r;
+            const uint64_t delta = uint64_t(g_delta[g]);
+            const uint64_t base =
+                uint64_t(g_t0sel[g]) + uint64_t(r - g_first) * delta;
+            int64_t *o = out_ts + r;
+            /* paired 16-B stores: closed-form generation is pure store
+               bandwidth; halving the store-instruction count lifted the
+               measured rate (the 1-row peel goes by the destination
+               address, so a caller's 8-B-aligned buffer is as good as a
+               16-B one).  One multiply per lane and segment; the loop
+               itself only adds. */
+            const int64_t head = int64_t((uintptr_t(o) >> 3) & 1);
+            if (head && threadIdx.x == 0) o[0] = int64_t(base);
+            const int64_t n2 = (cnt - head) >> 1;
+            longlong2 *op = (longlong2 *)(o + head);
+            uint64_t v0 =
+                base + (uint64_t(head) + 2 * uint64_t(threadIdx.x)) * delta;
+            const uint64_t step = 2 * uint64_t(blockDim.x) * delta;
+            for (int64_t q2 = threadIdx.x; q2 < n2; q2 += blockDim.x) {
+                longlong2 v;
+                v.x = int64_t(v0);
+                v.y = int64_t(v0 + delta);
+                op[q2] = v;
+                v0 += step;
+            }
+            if (((cnt - head) & 1) && threadIdx.x == 0)
+                o[cnt - 1] = int64_t(base + uint64_t(cnt - 1) * delta);
+            r = seg_end;
+            if (r >= r_end) break;
+            /* the next group is usually not empty: look before searching */
+            g = out_off[g + 2] > r ? g + 1
+                                   : ts_group_of(out_off, g + 2, ngroups, r);
         }
-        if (((cnt - head) & 1) && threadIdx.x == 0 && cnt > 0)
-            o[cnt - 1] = int64_t(base + uint64_t(cnt - 1) * uint64_t(delta));
     }
 }
 
@@ -3667,6 +3702,9 @@ struct SlotPages {
     bool agg_fused_ok = false;
 };
 
+/* fused-scan phase events (scan_fused_launch / scan_fused_wait) */
+enum { SEV_START, SEV_OFFS, SEV_TS, SEV_VAL, SEV_END, GS_NSEV };
+
 struct GsGroupSet {
     GsCtx *ctx = nullptr;
     uint8_t *d_blob = nullptr;
@@ -3686,7 +3724,7 @@ struct GsGroupSet {
                                           compacted output (rebuilt per scan) */
     int32_t *d_sgroup_first = nullptr; /* [nsgroups+1] first page-group idx */
     int64_t *d_blocksums = nullptr;    /* device-scan scratch */
-    hipEvent_t sev[6];                 /* fused-scan phase events */
+    hipEvent_t sev[GS_NSEV];           /* fused-scan phase events */
     bool sev_init = false;
     bool pending = false;              /* an async fused scan is in flight */
     int64_t *d_sp_start = nullptr;
@@ -4290,7 +4328,7 @@ void gs_groups_free(GsGroupSet *set) {
     if (set->d_sgroup_first) hipFree(set->d_sgroup_first);
     if (set->d_blocksums) hipFree(set->d_blocksums);
     if (set->sev_init)
-        for (int k = 0; k < 6; k++) hipEventDestroy(set->sev[k]);
+        for (int k = 0; k < GS_NSEV; k++) hipEventDestroy(set->sev[k]);
     hipFree(set->d_sp_start);
     hipFree(set->d_sp_cnt);
     hipFree(set->d_out_off);
@@ -4812,7 +4850,8 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                                   const int32_t *fields, int nf) {
     HIP_TRY(hipSetDevice(ctx->device));
     if (!set->sev_init) {
-        for (int k = 0; k < 6; k++) HIP_TRY(hipEventCreate(&set->sev[k]));
+        for (int k = 0; k < GS_NSEV; k++)
+            HIP_TRY(hipEventCreate(&set->sev[k]));
         set->sev_init = true;
     }
     hipEvent_t *ev = set->sev;
@@ -4837,7 +4876,7 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                   (SCAN_BLOCK * SCAN_ITEMS);
     if (nblocks > 2048)
         return fail(GS_ERR, "too many groups for the fused span scan");
-    HIP_TRY(hipEventRecord(ev[0], ctx->stream));
+    HIP_TRY(hipEventRecord(ev[SEV_START], ctx->stream));
     hipLaunchKernelGGL(k_spans_rle, dim3(grid_for(ng, 256)), dim3(256), 0,
                        ctx->stream, set->d_blob, ts_pages, ng,
                        spec->range.min_ts, spec->range.max_ts,
@@ -4851,12 +4890,15 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                        set->d_out_off, set->d_blocksums, nblocks);
     hipLaunchKernelGGL(k_scan_add, dim3(grid_for(ng, 256)), dim3(256), 0,
                        ctx->stream, ng, set->d_out_off, set->d_blocksums);
-    HIP_TRY(hipEventRecord(ev[1], ctx->stream));
-    hipLaunchKernelGGL(k_rle_ts_filtered, dim3(ng > 2048 ? 2048 : ng),
-                       dim3(256), 0, ctx->stream, set->d_blob, ts_pages, ng,
-                       set->d_sp_start, set->d_sp_cnt, set->d_out_off,
-                       spec->d_out_ts);
-    HIP_TRY(hipEventRecord(ev[2], ctx->stream));
+    HIP_TRY(hipEventRecord(ev[SEV_OFFS], ctx->stream));
+    /* at most every row of the set is selected: grid-stride beyond 2048
+       blocks, and blocks past the device-side total exit at once */
+    int64_t tiles = (set->total_rows + GS_TS_TILE - 1) / GS_TS_TILE;
+    tiles = tiles < 1 ? 1 : (tiles > 2048 ? 2048 : tiles);
+    hipLaunchKernelGGL(k_rle_ts_tiles, dim3(int(tiles)), dim3(256), 0,
+                       ctx->stream, set->d_out_off, ng, set->d_g_t0sel,
+                       set->d_g_delta, GS_TS_TILE, spec->d_out_ts);
+    HIP_TRY(hipEventRecord(ev[SEV_TS], ctx->stream));
     int nsg = set->nsgroups;
     if (spec->n_buckets > 0) {
         if (!spec->d_agg_max || !spec->d_agg_sum || !spec->d_agg_count)
@@ -4970,7 +5012,7 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                                set->d_sp_start, set->d_sp_cnt,
                                set->d_out_off, d_val_f, ctx->d_err, ag);
         }
-        if (f == 0) HIP_TRY(hipEventRecord(ev[3], ctx->stream));
+        if (f == 0) HIP_TRY(hipEventRecord(ev[SEV_VAL], ctx->stream));
         if (spec->n_buckets > 0) {
             if (agg_fused) {
                 hipLaunchKernelGGL(k_agg_fixup,
@@ -5020,14 +5062,13 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                                    size_t(f) * spec->n_buckets);
         }
     }
-    HIP_TRY(hipEventRecord(ev[4], ctx->stream));
-    HIP_TRY(hipEventRecord(ev[5], ctx->stream));
+    HIP_TRY(hipEventRecord(ev[SEV_END], ctx->stream));
     set->pending = true;
     return GS_OK;
 }
 
-/* Phase times from the six events of scan_fused_launch: filter = spans +
- * offset scan, decode_ts = k_rle_ts_filtered, decode_val = k_gor_active +
+/* Phase times from the events of scan_fused_launch: filter = spans +
+ * offset scan, decode_ts = k_rle_ts_tiles, decode_val = k_gor_active +
  * the Gorilla decode of field 0, agg = everything after it.  With the
  * fused aggregate (GS_AGG_FUSED, the default where the gate passes)
  * decode_val includes the in-kernel bucket accumulation and agg covers
@@ -5046,14 +5087,14 @@ static GsStatus scan_fused_wait(GsCtx *ctx, GsGroupSet *set,
                       hipMemcpyDeviceToHost));
     hipEvent_t *ev = set->sev;
     float ms;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[SEV_START], ev[SEV_OFFS]));
     result->ms_filter = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[SEV_OFFS], ev[SEV_TS]));
     result->ms_decode_ts = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[2], ev[3]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[SEV_TS], ev[SEV_VAL]));
     result->ms_decode_val = ms; /* nf>1: field 0 only */
     result->ms_compact = 0.0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[3], ev[4]));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[SEV_VAL], ev[SEV_END]));
     result->ms_agg = ms; /* fused aggregate: fix-up + merge only.
                             nf>1: field 0's agg + remaining fields */
     result->out_rows = acc;
