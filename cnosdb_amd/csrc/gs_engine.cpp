@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/cnosdb_gs.h"
 #include "gs_internal.h"
+#include "gs_gorilla.h"
 
 /* hipError_t returns are checked with HIP_TRY on every path that can fail
  * user-visibly; cleanup paths (hipFree/hipEventDestroy in destructors) and
@@ -139,8 +140,6 @@ struct DevS8b {
     }
 };
 
-
-#define GORILLA_SENTINEL 0x7ff8000000000ffULL
 
 /* ---------------------------------------------------------------- kernels */
 
@@ -279,289 +278,100 @@ __global__ void k_seq_i64(const uint8_t *__restrict__ blob,
     }
 }
 
-/* Gorilla f64 pages: one thread per page (the bitstream carries a strict
- * sequential dependency — float.rs:445-463; parallelism comes from the
- * page count).  The hot loop is a flat 128-bit-window parser: one 13-bit
- * peek covers ctrl bits + leading/meaningful, whole-word refills run over
- * the blob's tail pad with a bit-budget guard standing in for the
- * reference's end-of-block refill error — identical bit consumption and
- * identical error surface on truncated streams. */
-template <bool ALLVALID>
-__device__ __forceinline__ void gorilla_decode_page(
-    const uint8_t *data, uint32_t data_len, const uint8_t *bs, uint32_t n,
-    double *o, uint8_t *vd, unsigned *err) {
-    const uint8_t *s = data + 1;
-    uint32_t slen = data_len - 1;
-    if (slen < 9) { atomicOr(err, DERR_SHORT); return; }
-    uint64_t val = dev_be64(s + 1);
-    const uint8_t *p = s + 9;
-    int64_t budget = int64_t(slen - 9) * 8; /* bits the stream really holds */
-    uint64_t hi = 0, lo = 0;
-    int nb = 0; /* valid window bits (may exceed budget over the pad) */
-    uint32_t trailing_n = 0, meaningful_n = 64;
-    uint32_t r = 0;
-    bool bad = false;
-
-    auto emit = [&](uint64_t bits_) {
-        if (!ALLVALID) {
-            while (r < n && !dev_bit(bs, r)) { o[r] = 0.0; if (vd) vd[r] = 0; r++; }
-        }
-        if (r < n) {
-            o[r] = __longlong_as_double(int64_t(bits_));
-            if (vd) vd[r] = 1;
-            r++;
-        }
-    };
-    /* one-word prefetch: the load for the NEXT refill is issued as soon as
-       the previous word is consumed, so its latency hides under ~7 values
-       of ALU work instead of stalling every refill (the PMC profile showed
-       67% of wave cycles parked on exactly that wait) */
-    uint64_t nextw = dev_be64(p);
-    p += 8;
-    auto topup = [&]() { /* call only with nb < 64 (x >> 64 is UB/mod-64) */
-        uint64_t x = nextw;
-        nextw = dev_be64(p);
-        p += 8;
-        if (nb == 0) { hi = x; lo = 0; }
-        else { hi |= x >> nb; lo = x << (64 - nb); }
-        nb += 64;
-    };
-    auto consume = [&](unsigned k) { /* k in 1..=64 */
-        hi = (k == 64) ? lo : ((hi << k) | (lo >> (64 - k)));
-        lo = (k == 64) ? 0 : (lo << k);
-        nb -= int(k);
-        budget -= int64_t(k);
-    };
-
-    emit(val);
-    for (;;) {
-        if (nb < 64) topup(); /* >= 64 bits: enough for any single field */
-        if (budget <= 0) { bad = true; break; }
-        uint32_t top13 = uint32_t(hi >> 51);
-        if (!(top13 & 0x1000)) { /* ctrl 0: repeat */
-            consume(1);
-        } else {
-            if (top13 & 0x0800) { /* ctrl 11: new window */
-                uint32_t lead = (top13 >> 6) & 0x1f;
-                meaningful_n = top13 & 0x3f;
-                if (meaningful_n > 0) trailing_n = 64 - lead - meaningful_n;
-                else { trailing_n = 0; meaningful_n = 64; }
-                consume(13);
-            } else { /* ctrl 10: reuse window */
-                consume(2);
-            }
-            while (nb < int(meaningful_n)) topup();
-            uint64_t sbits = (meaningful_n == 64) ? hi : (hi >> (64 - meaningful_n));
-            consume(meaningful_n);
-            if (budget < 0) { bad = true; break; }
-            val ^= sbits << trailing_n;
-            if (val == GORILLA_SENTINEL) break;
-        }
-        emit(val); /* single store site per iteration */
-    }
-    if (bad) { atomicOr(err, DERR_SHORT); return; }
-    for (; r < n; r++) {
-        if (ALLVALID || dev_bit(bs, r)) { atomicOr(err, DERR_SHORT); break; }
-        o[r] = 0.0;
-        if (vd) vd[r] = 0;
-    }
-}
-
 #define GS_RING 16
 #define GS_GOR_BLOCK 256 /* 4 waves; RING 8/16/32 x block 128/256 swept: 16/256 optimal */
 
-/* --- Gorilla chunked decode (see DevGorChunk in gs_internal.h) ---
+/* --- Gorilla chunked decode (see DevGorChunk in gs_internal.h; the stream
+ * format and the window parser live in gs_gorilla.h) ---
  * k_gor_sync: one-time upload pre-pass.  One thread walks each multi-chunk
  * all-valid Gorilla page with the same window parser as decode (no value
  * stores) and records the parser state every chunk_rows values, so decode
  * can start mid-stream.  Errors are NOT raised here: a truncated or
  * early-sentinel page poisons its unrecorded chunks (bitpos past the
  * stream end), and the decode of that chunk raises DERR_SHORT exactly
- * where the page-sequential kernel would have — same error surface,
- * surfaced at decode/scan time like the reference's decode errors.
- *
- * Budget accounting (all Gorilla kernels here): instead of decrementing a
- * bit budget per value (2 ops/value + 2 checks/value on the round-1
- * parser), the cursor advances freely and correctness is enforced by
- * (a) a load clamp: words at/after p_clamp read as zero, so no access
- *     ever leaves the blob's 48-B tail pad;
- * (b) an overrun flag: once the window would hold only pad (entering
- *     word index >= W+2), the lane stops with DERR_SHORT — bounds every
- *     loop on corrupt input within ~128 pad bits;
- * (c) exact end checks, evaluated once per chunk (at the sentinel, or on
- *     completing a non-final chunk): bits consumed > total_bits means the
- *     parse ran past the real stream -> DERR_SHORT, reproducing the
- *     reference's "unexpected end of block" (float.rs:462) surface. */
+ * where a page-sequential decode would have — same error surface,
+ * surfaced at decode/scan time like the reference's decode errors. */
 __global__ void k_gor_sync(const uint8_t *__restrict__ blob,
                            const DevPage *__restrict__ pages, int npages,
                            const int32_t *__restrict__ chunk_base,
                            DevGorChunk *__restrict__ chunks,
-                           uint32_t chunk_rows, int il_stride) {
+                           uint32_t chunk_rows) {
     for (int pi = blockIdx.x * blockDim.x + threadIdx.x; pi < npages;
          pi += gridDim.x * blockDim.x) {
         DevPage pg = pages[pi];
         int cb = chunk_base[pi];
         int nch = chunk_base[pi + 1] - cb;
         if (nch <= 1) continue; /* single chunk: decode reads the header */
-        /* chunk k of page pi lives at cb+k (page-major) or
-           k*il_stride+pi (interleaved) */
-        auto cidx = [&](int k) {
-            return il_stride ? k * il_stride + pi : cb + k;
-        };
-        const uint8_t *data = blob + pg.data_off;
         int next_k = 1;
+        /* value-initialised, here and in the three kernels below: left
+           indeterminate on the short-page path, the state cost registers
+           and k_gor_sync_null recorded wrong tables on a set of 625,000
+           pages ("One parser for the four cold kernels") */
+        GorChunkState st{};
+        uint32_t r = 1; /* header value = row 0 */
         bool ok = false;
-        if (pg.data_len >= 10) {
-            int64_t total_bits = int64_t(pg.data_len - 10) * 8;
-            const uint8_t *stream = data + 10;
-            uint64_t W = (uint64_t(total_bits) + 63) >> 6;
-            const uint8_t *p_clamp = stream + 8 * W + 24;
-            const uint8_t *p_over = stream + 8 * W + 40;
-            uint64_t val = dev_be64(data + 2);
-            const uint8_t *p = stream;
-            uint64_t hi = 0, lo = 0;
-            int nb = 0;
-            uint32_t trailing = 0, meaningful = 64;
-            uint32_t r = 1; /* header value = row 0 */
-            bool over = false;
-            uint64_t nextw = dev_be64(p);
-            uint64_t nextw2 = dev_be64(p + 8);
-            p += 16;
-            auto topup = [&]() { /* only with nb < 64 */
-                uint64_t x = nextw;
-                nextw = nextw2;
-                over |= (p >= p_over);
-                nextw2 = (p < p_clamp) ? dev_be64(p) : 0;
-                p += 8;
-                if (nb == 0) { hi = x; lo = 0; }
-                else { hi |= x >> nb; lo = x << (64 - nb); }
-                nb += 64;
-            };
-            auto consume = [&](unsigned k) { /* k in 1..=64 */
-                hi = (k == 64) ? lo : ((hi << k) | (lo >> (64 - k)));
-                lo = (k == 64) ? 0 : (lo << k);
-                nb -= int(k);
-            };
+        if (gor_start(st, blob + pg.data_off, pg.data_len)) {
             ok = true;
             for (;;) {
                 if (r == uint32_t(next_k) * chunk_rows) {
-                    int64_t used = int64_t(p - stream) * 8 - 128 - nb;
-                    if (used > total_bits) { ok = false; break; }
-                    DevGorChunk &c = chunks[cidx(next_k)];
-                    c.bitpos = uint64_t(used);
-                    c.val = val;
-                    c.trailing = uint8_t(trailing);
-                    c.meaningful = uint8_t(meaningful);
+                    if (gor_used_bits(st) > st.total_bits) {
+                        ok = false;
+                        break;
+                    }
+                    gor_record(st, chunks[cb + next_k]);
                     /* the previous chunk's whole range is now known
                        decodable: the filtered kernel may stop it early */
-                    chunks[cidx(next_k - 1)].flags = GORF_SAFE_STOP;
+                    chunks[cb + next_k - 1].flags = GORF_SAFE_STOP;
                     next_k++;
                     if (next_k == nch) break; /* tail chunk parses itself */
                 }
-                if (nb < 64) topup();
-                if (over) { ok = false; break; }
-                uint32_t top13 = uint32_t(hi >> 51);
-                if (!(top13 & 0x1000)) { /* ctrl 0: repeat */
-                    consume(1);
-                } else {
-                    unsigned shift = 2;
-                    if (top13 & 0x0800) { /* ctrl 11: new window */
-                        uint32_t lead = (top13 >> 6) & 0x1f;
-                        meaningful = top13 & 0x3f;
-                        if (meaningful > 0) trailing = 64 - lead - meaningful;
-                        else { trailing = 0; meaningful = 64; }
-                        shift = 13;
-                    }
-                    unsigned need = shift + meaningful; /* <= 77 */
-                    uint64_t sb;
-                    if (int(need) <= nb) { /* window holds the whole value */
-                        uint64_t w = (hi << shift) | (lo >> (64 - shift));
-                        sb = (meaningful == 64) ? w : (w >> (64 - meaningful));
-                        if (need <= 64) consume(need);
-                        else { consume(shift); consume(meaningful); }
-                    } else { /* short window: two-step (topup needs nb<64) */
-                        consume(shift);
-                        while (nb < int(meaningful)) topup();
-                        sb = (meaningful == 64) ? hi : (hi >> (64 - meaningful));
-                        consume(meaningful);
-                    }
-                    val ^= sb << trailing;
-                    /* sentinel before the last sync point: rows missing */
-                    if (val == GORILLA_SENTINEL) { ok = false; break; }
+                if (st.nb < 64) gor_topup(st);
+                if (st.over) { ok = false; break; }
+                /* sentinel before the last sync point: rows missing */
+                if (gor_parse(st) && st.val == GORILLA_SENTINEL) {
+                    ok = false;
+                    break;
                 }
                 r++;
             }
         }
-        if (!ok) { /* poison unrecorded chunks -> DERR_SHORT at decode */
-            for (int k = next_k; k < nch; k++) {
-                DevGorChunk &c = chunks[cidx(k)];
-                c.bitpos = uint64_t(pg.data_len) * 8;
-                c.val = 0;
-                c.trailing = 0;
-                c.meaningful = 64;
-                c.flags = 0;
-            }
-        }
+        if (!ok) /* poison unrecorded chunks -> DERR_SHORT at decode */
+            for (int k = next_k; k < nch; k++)
+                gor_poison(chunks[cb + k], pg.data_len);
     }
 }
 
-/* Parser window state of one chunk, positioned at DevGorChunk.bitpos. */
-struct GorChunkState {
-    const uint8_t *p;       /* next 8-byte word to prefetch */
-    const uint8_t *stream;  /* bitstream start (page data + 10) */
-    const uint8_t *p_clamp; /* loads at/after here read as zero */
-    const uint8_t *p_over;  /* reaching here = stream overrun */
-    uint64_t hi, lo, nextw, nextw2;
-    uint64_t val;
-    int64_t total_bits;
-    int nb;
-    uint32_t trailing, meaningful;
-    bool bad;
-};
-
-__device__ __forceinline__ GorChunkState
-gor_chunk_init(const uint8_t *__restrict__ blob, const DevGorChunk &c) {
-    GorChunkState st;
-    st.bad = false;
-    const uint8_t *data = blob + c.data_off;
-    /* page data: [enc=6][0x10][first f64 BE][bitstream] (float.rs:418-444) */
-    if (c.data_len < 10) { st.bad = true; return st; }
-    const uint8_t *stream = data + 10;
-    st.stream = stream;
-    st.total_bits = int64_t(c.data_len - 10) * 8;
-    uint64_t W = (uint64_t(st.total_bits) + 63) >> 6;
-    st.p_clamp = stream + 8 * W + 24;
-    st.p_over = stream + 8 * W + 40;
-    if (c.row0 == 0) {
-        st.val = dev_be64(data + 2);
-        st.trailing = 0;
-        st.meaningful = 64;
-        st.hi = 0;
-        st.lo = 0;
-        st.nb = 0;
-        st.nextw = dev_be64(stream);
-        st.nextw2 = dev_be64(stream + 8);
-        st.p = stream + 16;
-    } else {
-        if (int64_t(c.bitpos) >= st.total_bits) { /* poisoned / truncated */
-            st.bad = true;
-            return st;
+/* One wave flushes its LDS ring: every lane posts {element offset into
+ * out, staged count} of its run, then the wave stores all 64 runs with
+ * chunk-contiguous coalesced stores.  4 source lanes per store instruction:
+ * lane = (sq:2, idx:4), sq picks the source sub-lane, idx the ring slot,
+ * reads batched 4 deep before their stores.  An offset, not a pointer: a
+ * pointer that travels through LDS loses its address space and the stores
+ * become flat (see k_gor_chunks_filtered, which keeps its own copy of this
+ * loop next to its output cursor). */
+__device__ __forceinline__ void gor_ring_flush(double (*rslot)[64 + 1],
+                                               uint64_t (*fd)[2], int lane,
+                                               double *__restrict__ out,
+                                               uint64_t o_off, int rfill) {
+    const int f_idx = lane & (GS_RING - 1);
+    const int f_sq = lane / GS_RING;
+    fd[lane][0] = o_off;
+    fd[lane][1] = uint64_t(rfill);
+    __builtin_amdgcn_wave_barrier();
+    constexpr int SRCP = 64 / GS_RING; /* sources per store */
+    for (int src0 = 0; src0 < 64; src0 += SRCP * 4) {
+        double vbuf[4];
+        uint64_t ob[4];
+        int cnt[4];
+        for (int t = 0; t < 4; t++) {
+            int src = src0 + f_sq + t * SRCP;
+            vbuf[t] = rslot[f_idx][src];
+            ob[t] = fd[src][0];
+            cnt[t] = int(fd[src][1]);
         }
-        st.val = c.val;
-        st.trailing = c.trailing;
-        st.meaningful = c.meaningful;
-        const uint8_t *p = stream + (c.bitpos >> 6) * 8;
-        unsigned rem = unsigned(c.bitpos & 63);
-        uint64_t w0 = dev_be64(p);
-        p += 8;
-        st.hi = (rem == 0) ? w0 : (w0 << rem);
-        st.lo = 0;
-        st.nb = int(64 - rem);
-        st.nextw = dev_be64(p);
-        st.nextw2 = dev_be64(p + 8);
-        st.p = p + 16;
+        for (int t = 0; t < 4; t++)
+            if (f_idx < cnt[t]) out[ob[t] + uint64_t(f_idx)] = vbuf[t];
     }
-    return st;
 }
 
 /* Chunk-parallel Gorilla decode with LDS-staged output: each lane decodes
@@ -591,130 +401,50 @@ __global__ void k_gor_chunks(const uint8_t *__restrict__ blob,
         /* branch-free prologue: clamp to chunk 0 so every load issues
            unconditionally (see k_gor_chunks_filtered) */
         DevGorChunk ch = chunks[have ? ci : 0];
-        double *o = out + ch.row_off;
         uint32_t r = ch.row0;
         uint32_t end = ch.row0 + ch.cnt;
-        if (ch.cnt == 0) have = false; /* interleave-padding entry */
-        GorChunkState st = gor_chunk_init(blob, ch);
+        if (ch.cnt == 0) have = false; /* the one chunk of a zero-row page */
+        GorChunkState st{};
+        gor_position(st, blob, ch);
         int rfill = 0;
-        bool done = !have, over = false;
+        bool done = !have;
         if (!have) { r = 0; end = 0; }
         if (have && st.bad) { atomicOr(err, DERR_SHORT); done = true; }
-        auto topup = [&]() { /* only with nb < 64 */
-            uint64_t x = st.nextw;
-            st.nextw = st.nextw2;
-            over |= (st.p >= st.p_over);
-            st.nextw2 = (st.p < st.p_clamp) ? dev_be64(st.p) : 0;
-            st.p += 8;
-            if (st.nb == 0) { st.hi = x; st.lo = 0; }
-            else { st.hi |= x >> st.nb; st.lo = x << (64 - st.nb); }
-            st.nb += 64;
-        };
-        auto consume = [&](unsigned k) { /* k in 1..=64 */
-            st.hi = (k == 64) ? st.lo : ((st.hi << k) | (st.lo >> (64 - k)));
-            st.lo = (k == 64) ? 0 : (st.lo << k);
-            st.nb -= int(k);
-        };
-        auto used_bits = [&]() {
-            return int64_t(st.p - st.stream) * 8 - 128 - st.nb;
-        };
-        auto fd = fdesc[wv];
-        const int f_idx = lane & (GS_RING - 1);
-        const int f_sq = lane / GS_RING;
-        double *rcur = &rslot[0][lane]; /* strength-reduced ring
-                                           cursor (row stride 65*8 B) */
         auto flush = [&]() {
-            fd[lane][0] = (uint64_t)(uintptr_t)(o + (int64_t(r) - rfill));
-            fd[lane][1] = uint64_t(rfill);
-            __builtin_amdgcn_wave_barrier();
-            constexpr int SRCP = 64 / GS_RING; /* sources per store */
-            for (int src0 = 0; src0 < 64; src0 += SRCP * 4) {
-                double vbuf[4];
-                uint64_t ob[4];
-                int cnt[4];
-                for (int t = 0; t < 4; t++) {
-                    int src = src0 + f_sq + t * SRCP;
-                    vbuf[t] = rslot[f_idx][src];
-                    ob[t] = fd[src][0];
-                    cnt[t] = int(fd[src][1]);
-                }
-                for (int t = 0; t < 4; t++)
-                    if (f_idx < cnt[t])
-                        ((double *)(uintptr_t)ob[t])[f_idx] = vbuf[t];
-            }
+            gor_ring_flush(rslot, fdesc[wv], lane, out,
+                           uint64_t(ch.row_off + int64_t(r) - rfill), rfill);
             rfill = 0;
-            rcur = &rslot[0][lane];
         };
         if (!done && ch.row0 == 0 && r < end) { /* header value = row 0 */
-            *rcur = __longlong_as_double((long long)st.val);
-            rcur += 65;
+            rslot[rfill][lane] = __longlong_as_double((long long)st.val);
             rfill++;
             r++;
         }
         unsigned it = 1; /* header stage counts toward the first cadence */
         while (!__all(done)) {
             if (!done) {
-                if (st.nb < 64) topup();
-                if (over) { atomicOr(err, DERR_SHORT); done = true; }
+                if (st.nb < 64) gor_topup(st);
+                if (st.over) { atomicOr(err, DERR_SHORT); done = true; }
             }
             if (!done) {
-                uint32_t top13 = uint32_t(st.hi >> 51);
                 bool stg = true;
-                {
-                    /* uniform path (no repeat/xor branch): a repeat is an
-                       XOR value with 0 meaningful bits (sb=0), so every
-                       lane runs the same straight-line code and the wave
-                       diverges only on the rare need>64 case — measured
-                       the round-1 two-branch parse at ~20% VALU
-                       utilization, divergence being the dominant loss */
-                    unsigned bit0 = (top13 >> 12) & 1; /* 1 = XOR value */
-                    unsigned bit1 = (top13 >> 11) & 1; /* 1 = new window */
-                    unsigned nw = bit0 & bit1;
-                    uint32_t lead = (top13 >> 6) & 0x1f;
-                    uint32_t mg_raw = top13 & 0x3f;
-                    uint32_t mg_new = mg_raw ? mg_raw : 64;
-                    uint32_t tr_new = mg_raw ? (64 - lead - mg_raw) : 0;
-                    st.meaningful = nw ? mg_new : st.meaningful;
-                    st.trailing = nw ? tr_new : st.trailing;
-                    unsigned shift = bit0 ? (bit1 ? 13u : 2u) : 1u;
-                    unsigned m_eff = bit0 ? st.meaningful : 0u;
-                    unsigned need = shift + m_eff;
-                    uint64_t sb;
-                    if (__builtin_expect(need < 64, 1)) {
-                        /* nb >= 64 after the loop-top topup; need < 64
-                           keeps the consume branch-free (no k==64 case) */
-                        uint64_t w =
-                            (st.hi << shift) | (st.lo >> (64 - shift));
-                        sb = m_eff ? (w >> ((64 - m_eff) & 63)) : 0;
-                        st.hi = (st.hi << need) | (st.lo >> (64 - need));
-                        st.lo <<= need;
-                        st.nb -= int(need);
-                    } else { /* m_eff >= 51: rare */
-                        consume(shift);
-                        while (st.nb < int(m_eff)) topup();
-                        sb = (m_eff == 64) ? st.hi
-                                           : (st.hi >> (64 - m_eff));
-                        consume(m_eff);
-                    }
-                    st.val ^= sb << st.trailing;
-                    if (bit0 && st.val == GORILLA_SENTINEL) {
-                        done = true;
-                        stg = false;
-                        if (used_bits() > st.total_bits)
-                            atomicOr(err, DERR_SHORT);
-                    }
+                if (gor_parse(st) && st.val == GORILLA_SENTINEL) {
+                    done = true;
+                    stg = false;
+                    if (gor_used_bits(st) > st.total_bits)
+                        atomicOr(err, DERR_SHORT);
                 }
                 if (stg && r < end) {
-                    *rcur = __longlong_as_double((long long)st.val);
-                    rcur += 65;
+                    rslot[rfill][lane] =
+                        __longlong_as_double((long long)st.val);
                     rfill++;
                     r++;
                     /* non-last chunk: all rows produced, stop; the last
-                       chunk keeps parsing to the sentinel like the page-
-                       sequential kernel (a missing sentinel is an error) */
+                       chunk keeps parsing to the sentinel like a page-
+                       sequential decode (a missing sentinel is an error) */
                     if (r == end && !ch.last) {
                         done = true;
-                        if (used_bits() > st.total_bits)
+                        if (gor_used_bits(st) > st.total_bits)
                             atomicOr(err, DERR_SHORT);
                     }
                 }
@@ -750,107 +480,46 @@ __global__ void k_gor_sync_null(const uint8_t *__restrict__ blob,
         int cb = chunk_base[pi];
         int nch = chunk_base[pi + 1] - cb;
         if (nch <= 1) continue;
-        const uint8_t *data = blob + pg.data_off;
         const uint8_t *bs = blob + pg.bitset_off;
         int next_k = 1;
-        bool ok = false;
         bool sent_seen = false;
-        if (pg.data_len >= 10) {
-            int64_t total_bits = int64_t(pg.data_len - 10) * 8;
-            const uint8_t *stream = data + 10;
-            uint64_t W = (uint64_t(total_bits) + 63) >> 6;
-            const uint8_t *p_clamp = stream + 8 * W + 24;
-            const uint8_t *p_over = stream + 8 * W + 40;
-            uint64_t val = dev_be64(data + 2); /* pending for 1st set row */
-            const uint8_t *p = stream;
-            uint64_t hi = 0, lo = 0;
-            int nb = 0;
-            uint32_t trailing = 0, meaningful = 64;
-            uint32_t r = 0; /* ROW cursor */
-            bool over = false;
-            uint64_t nextw = dev_be64(p);
-            uint64_t nextw2 = dev_be64(p + 8);
-            p += 16;
-            auto topup = [&]() {
-                uint64_t x = nextw;
-                nextw = nextw2;
-                over |= (p >= p_over);
-                nextw2 = (p < p_clamp) ? dev_be64(p) : 0;
-                p += 8;
-                if (nb == 0) { hi = x; lo = 0; }
-                else { hi |= x >> nb; lo = x << (64 - nb); }
-                nb += 64;
-            };
-            auto consume = [&](unsigned k) {
-                hi = (k == 64) ? lo : ((hi << k) | (lo >> (64 - k)));
-                lo = (k == 64) ? 0 : (lo << k);
-                nb -= int(k);
-            };
+        GorChunkState st{}; /* val: pending for the 1st set row */
+        uint32_t r = 0; /* ROW cursor */
+        bool ok = false;
+        if (gor_start(st, blob + pg.data_off, pg.data_len)) {
             ok = true;
             for (;;) {
                 if (r == uint32_t(next_k) * chunk_rows) {
-                    int64_t used = int64_t(p - stream) * 8 - 128 - nb;
-                    if (!sent_seen && used > total_bits) { ok = false; break; }
+                    if (!sent_seen && gor_used_bits(st) > st.total_bits) {
+                        ok = false;
+                        break;
+                    }
                     DevGorChunk &c = chunks[cb + next_k];
-                    c.bitpos = uint64_t(used);
-                    c.val = val;
-                    c.trailing = uint8_t(trailing);
-                    c.meaningful = uint8_t(meaningful);
+                    gor_record(st, c);
                     c.flags = sent_seen ? GORF_SENT_SEEN : 0;
                     next_k++;
                     if (next_k == nch) break;
                     if (sent_seen) continue; /* tail: just mark chunks */
                 }
                 if (sent_seen) { r++; continue; } /* walk rows to boundary */
-                if (nb < 64) topup();
-                if (over) { ok = false; break; }
+                if (st.nb < 64) gor_topup(st);
+                if (st.over) { ok = false; break; }
+                /* a set row consumes the pending value: parse the next one */
                 if (dev_bit(bs, r)) {
-                    /* this set row consumes the pending value: parse the
-                       next one (uniform path, see k_gor_chunks) */
-                    uint32_t top13 = uint32_t(hi >> 51);
-                    unsigned bit0 = (top13 >> 12) & 1;
-                    unsigned bit1 = (top13 >> 11) & 1;
-                    unsigned nw = bit0 & bit1;
-                    uint32_t lead = (top13 >> 6) & 0x1f;
-                    uint32_t mg_raw = top13 & 0x3f;
-                    uint32_t mg_new = mg_raw ? mg_raw : 64;
-                    uint32_t tr_new = mg_raw ? (64 - lead - mg_raw) : 0;
-                    meaningful = nw ? mg_new : meaningful;
-                    trailing = nw ? tr_new : trailing;
-                    unsigned shift = bit0 ? (bit1 ? 13u : 2u) : 1u;
-                    unsigned m_eff = bit0 ? meaningful : 0u;
-                    unsigned need = shift + m_eff;
-                    uint64_t sb;
-                    if (need <= 64) {
-                        uint64_t w = (hi << shift) | (lo >> (64 - shift));
-                        sb = m_eff ? (w >> ((64 - m_eff) & 63)) : 0;
-                        consume(need);
-                    } else {
-                        consume(shift);
-                        while (nb < int(m_eff)) topup();
-                        sb = (m_eff == 64) ? hi : (hi >> (64 - m_eff));
-                        consume(m_eff);
-                    }
-                    val ^= sb << trailing;
-                    if (bit0 && val == GORILLA_SENTINEL) {
-                        int64_t used = int64_t(p - stream) * 8 - 128 - nb;
-                        if (used > total_bits) { ok = false; break; }
+                    if (gor_parse(st) && st.val == GORILLA_SENTINEL) {
+                        if (gor_used_bits(st) > st.total_bits) {
+                            ok = false;
+                            break;
+                        }
                         sent_seen = true;
                     }
                 }
                 r++;
             }
         }
-        if (!ok) { /* poison unrecorded chunks -> DERR_SHORT at decode */
-            for (int k = next_k; k < nch; k++) {
-                DevGorChunk &c = chunks[cb + k];
-                c.bitpos = uint64_t(pg.data_len) * 8;
-                c.val = 0;
-                c.trailing = 0;
-                c.meaningful = 64;
-                c.flags = 0;
-            }
-        }
+        if (!ok) /* poison unrecorded chunks -> DERR_SHORT at decode */
+            for (int k = next_k; k < nch; k++)
+                gor_poison(chunks[cb + k], pg.data_len);
     }
 }
 
@@ -875,7 +544,6 @@ __global__ void k_gor_chunks_null(const uint8_t *__restrict__ blob,
         bool have = ci < nchunks;
         DevGorChunk ch = chunks[have ? ci : 0];
         const uint8_t *bs = blob + ch.bitset_off;
-        double *o = out + ch.row_off;
         uint32_t r = ch.row0;
         /* per-8-row bitset byte, prefetched one ahead like the stream
            refills (measured neutral: the kernel is ~72% memory-parked
@@ -888,102 +556,31 @@ __global__ void k_gor_chunks_null(const uint8_t *__restrict__ blob,
         uint32_t bb_next = bs[bb_idx + 1];
         uint32_t end = ch.row0 + ch.cnt;
         bool sent_seen = (ch.flags & GORF_SENT_SEEN) != 0;
-        GorChunkState st;
-        st.bad = false;
-        if (sent_seen) { /* tail chunk after the sentinel: nulls only */
-            st.p = st.stream = st.p_clamp = st.p_over = nullptr;
-            st.hi = st.lo = st.nextw = st.nextw2 = st.val = 0;
-            st.total_bits = 0;
-            st.nb = 0;
-            st.trailing = 0;
-            st.meaningful = 64;
-        } else {
-            st = gor_chunk_init(blob, ch);
-        }
+        /* a tail chunk after the sentinel holds nulls only and never
+           touches the stream: its state stays zero */
+        GorChunkState st{};
+        if (!sent_seen) gor_position(st, blob, ch);
         int rfill = 0;
-        bool done = !have, over = false;
+        bool done = !have;
         if (!have) { r = 0; end = 0; }
         if (have && st.bad) { atomicOr(err, DERR_SHORT); done = true; }
-        auto topup = [&]() {
-            uint64_t x = st.nextw;
-            st.nextw = st.nextw2;
-            over |= (st.p >= st.p_over);
-            st.nextw2 = (st.p < st.p_clamp) ? dev_be64(st.p) : 0;
-            st.p += 8;
-            if (st.nb == 0) { st.hi = x; st.lo = 0; }
-            else { st.hi |= x >> st.nb; st.lo = x << (64 - st.nb); }
-            st.nb += 64;
-        };
-        auto consume = [&](unsigned k) {
-            st.hi = (k == 64) ? st.lo : ((st.hi << k) | (st.lo >> (64 - k)));
-            st.lo = (k == 64) ? 0 : (st.lo << k);
-            st.nb -= int(k);
-        };
-        auto used_bits = [&]() {
-            return int64_t(st.p - st.stream) * 8 - 128 - st.nb;
-        };
-        auto parse_one = [&]() { /* uniform path; updates st / sent_seen */
-            uint32_t top13 = uint32_t(st.hi >> 51);
-            unsigned bit0 = (top13 >> 12) & 1;
-            unsigned bit1 = (top13 >> 11) & 1;
-            unsigned nw = bit0 & bit1;
-            uint32_t lead = (top13 >> 6) & 0x1f;
-            uint32_t mg_raw = top13 & 0x3f;
-            uint32_t mg_new = mg_raw ? mg_raw : 64;
-            uint32_t tr_new = mg_raw ? (64 - lead - mg_raw) : 0;
-            st.meaningful = nw ? mg_new : st.meaningful;
-            st.trailing = nw ? tr_new : st.trailing;
-            unsigned shift = bit0 ? (bit1 ? 13u : 2u) : 1u;
-            unsigned m_eff = bit0 ? st.meaningful : 0u;
-            unsigned need = shift + m_eff;
-            uint64_t sb;
-            if (__builtin_expect(need < 64, 1)) {
-                uint64_t w = (st.hi << shift) | (st.lo >> (64 - shift));
-                sb = m_eff ? (w >> ((64 - m_eff) & 63)) : 0;
-                st.hi = (st.hi << need) | (st.lo >> (64 - need));
-                st.lo <<= need;
-                st.nb -= int(need);
-            } else {
-                consume(shift);
-                while (st.nb < int(m_eff)) topup();
-                sb = (m_eff == 64) ? st.hi : (st.hi >> (64 - m_eff));
-                consume(m_eff);
-            }
-            st.val ^= sb << st.trailing;
-            if (bit0 && st.val == GORILLA_SENTINEL) {
-                if (used_bits() > st.total_bits) atomicOr(err, DERR_SHORT);
+        auto parse_one = [&]() { /* updates st / sent_seen */
+            if (gor_parse(st) && st.val == GORILLA_SENTINEL) {
+                if (gor_used_bits(st) > st.total_bits)
+                    atomicOr(err, DERR_SHORT);
                 sent_seen = true;
             }
         };
-        auto fd = fdesc[wv];
-        const int f_idx = lane & (GS_RING - 1);
-        const int f_sq = lane / GS_RING;
         auto flush = [&]() {
-            fd[lane][0] = (uint64_t)(uintptr_t)(o + (int64_t(r) - rfill));
-            fd[lane][1] = uint64_t(rfill);
-            __builtin_amdgcn_wave_barrier();
-            constexpr int SRCP = 64 / GS_RING;
-            for (int src0 = 0; src0 < 64; src0 += SRCP * 4) {
-                double vbuf[4];
-                uint64_t ob[4];
-                int cnt[4];
-                for (int t = 0; t < 4; t++) {
-                    int src = src0 + f_sq + t * SRCP;
-                    vbuf[t] = rslot[f_idx][src];
-                    ob[t] = fd[src][0];
-                    cnt[t] = int(fd[src][1]);
-                }
-                for (int t = 0; t < 4; t++)
-                    if (f_idx < cnt[t])
-                        ((double *)(uintptr_t)ob[t])[f_idx] = vbuf[t];
-            }
+            gor_ring_flush(rslot, fdesc[wv], lane, out,
+                           uint64_t(ch.row_off + int64_t(r) - rfill), rfill);
             rfill = 0;
         };
         unsigned it = 0;
         while (!__all(done)) {
             if (!done && !sent_seen) {
-                if (st.nb < 64) topup();
-                if (over) { atomicOr(err, DERR_SHORT); done = true; }
+                if (st.nb < 64) gor_topup(st);
+                if (st.over) { atomicOr(err, DERR_SHORT); done = true; }
             }
             if (!done) {
                 if (r < end) {
@@ -1015,7 +612,7 @@ __global__ void k_gor_chunks_null(const uint8_t *__restrict__ blob,
                             if (!ch.last) {
                                 done = true;
                                 if (!sent_seen &&
-                                    used_bits() > st.total_bits)
+                                    gor_used_bits(st) > st.total_bits)
                                     atomicOr(err, DERR_SHORT);
                             }
                             /* last chunk: keep draining to the sentinel */
@@ -1099,10 +696,11 @@ __global__ void k_seq_f64(const uint8_t *__restrict__ blob,
             continue;
         }
         if (enc != GS_ENC_GORILLA) { atomicOr(err, DERR_FORMAT); continue; }
-        if (pg.all_valid)
-            gorilla_decode_page<true>(data, pg.data_len, bs, n, o, vd, err);
-        else
-            gorilla_decode_page<false>(data, pg.data_len, bs, n, o, vd, err);
+        /* Only streams too short to hold the header value arrive here:
+           this kernel runs on F64 slots alone, and gs_groups_upload files
+           every F64 Gorilla page with data_len >= 10 under PC_GOR or
+           PC_GORN (the chunked kernels), whatever its validity. */
+        atomicOr(err, DERR_SHORT);
     }
 }
 
@@ -2977,7 +2575,8 @@ __global__ void k_gor_chunks_filtered(const uint8_t *__restrict__ blob,
             stage_hi > sel_lo ? uint32_t(stage_hi - sel_lo) : 0u;
         uint64_t o_cur = uint64_t(out_off[ch.grp]) +
                          uint64_t((r > sel_lo ? r : sel_lo) - sel_lo);
-        GorChunkState st = gor_chunk_init(blob, ch);
+        GorChunkState st;
+        gor_position(st, blob, ch);
         bool live = have && ch.cnt > 0;
         if (live && st.bad) { atomicOr(err, DERR_SHORT); live = false; }
         /* Refill state.  The 128-bit window hi:lo holds nb valid bits;
@@ -4126,38 +3725,6 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
                 acc += int32_t(nch);
             }
             cbase[sp.n[pc]] = acc;
-            /* layout experiment (GS_GOR_ORDER=interleave, PC_GOR only):
-               chunk-position-major table — a wave's 64 lanes then write
-               64 DIFFERENT series' output regions instead of one series'
-               contiguous region (DRAM channel spread).  Ragged pages are
-               padded with cnt=0 entries the decode kernels skip. */
-            static int il = [] {
-                const char *e = getenv("GS_GOR_ORDER");
-                return e && strcmp(e, "interleave") == 0;
-            }();
-            int il_stride = 0;
-            if (il && gcls == 0 && sp.n[pc] > 0) {
-                uint32_t maxc = 0;
-                for (int i = 0; i < sp.n[pc]; i++)
-                    maxc = uint32_t(cbase[i + 1] - cbase[i]) > maxc
-                               ? uint32_t(cbase[i + 1] - cbase[i]) : maxc;
-                if (maxc > 1) {
-                    il_stride = sp.n[pc];
-                    std::vector<DevGorChunk> h2(size_t(maxc) * sp.n[pc]);
-                    for (auto &c : h2) {
-                        c = DevGorChunk{};
-                        c.cnt = 0;
-                        c.slot = GOR_NO_SLOT;
-                    }
-                    for (int i = 0; i < sp.n[pc]; i++) {
-                        int nchi = cbase[i + 1] - cbase[i];
-                        for (int k = 0; k < nchi; k++)
-                            h2[size_t(k) * sp.n[pc] + i] = hch[cbase[i] + k];
-                    }
-                    hch.swap(h2);
-                    acc = int32_t(hch.size());
-                }
-            }
             DevGorChunk **dchp = gcls == 0 ? &sp.d_gor_chunks
                                            : &sp.d_gorn_chunks;
             int32_t **dcbp = gcls == 0 ? &sp.d_gor_chunk_base
@@ -4184,8 +3751,7 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
                 hipLaunchKernelGGL(k_gor_sync,
                                    dim3(grid_for(sp.n[pc], 256)), dim3(256),
                                    0, ctx->stream, set->d_blob, sp.dev[pc],
-                                   sp.n[pc], *dcbp, *dchp, chunk_rows,
-                                   il_stride);
+                                   sp.n[pc], *dcbp, *dchp, chunk_rows);
             else
                 hipLaunchKernelGGL(k_gor_sync_null,
                                    dim3(grid_for(sp.n[pc], 256)), dim3(256),
@@ -4276,8 +3842,7 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
         t.resize(hsg.size() + 1);
         for (size_t s = 0; s <= hsg.size(); s++)
             t[s] = sp.gor_grp_cbase[sgfirst[s]];
-        /* (the interleaved layout experiment pads the table, so the
-           ordinals may number fewer than n_gor_chunks, never more) */
+        /* (the ordinals number exactly the table's chunks) */
         if (t[0] != 0 || t[hsg.size()] > sp.n_gor_chunks)
             sp.agg_fused_ok = false;
         for (size_t s = 0; s < hsg.size() && sp.agg_fused_ok; s++) {

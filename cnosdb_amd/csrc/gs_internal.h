@@ -68,7 +68,7 @@ struct DevGorChunk {
     uint32_t slot;       /* PC_GOR: chunk ordinal in PAGE-GROUP order (the
                             table itself is sorted longest-page-first), the
                             index of this chunk's head/tail aggregate pieces;
-                            GOR_NO_SLOT for padding entries and PC_GORN.
+                            GOR_NO_SLOT for PC_GORN.
                             Occupies former tail padding: sizeof stays 64. */
 };
 #define GOR_NO_SLOT 0xffffffffu

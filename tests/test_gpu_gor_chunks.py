@@ -40,6 +40,21 @@ def _walk(n, r=rng, repeat_frac=0.3):
     return v
 
 
+def _alternating(n):
+    """0x3FF0000000000001 and 0xBFF0000000000000 by turns: every XOR has
+    all 64 bits meaningful, which the 6-bit length field writes as 0."""
+    bits = np.where(np.arange(n) % 2 == 0, 0x3FF0000000000001,
+                    0xBFF0000000000000).astype(np.uint64)
+    return bits.view(np.float64)
+
+
+def _full_precision(n):
+    """Doubles with all mantissa bits in use: XOR values of 51 and more
+    meaningful bits, the parser's rare two-step path.  Own generator, so
+    the other tests' draws from rng stay what they were."""
+    return np.random.default_rng(20251021).uniform(0, 1e3, n)
+
+
 def _upload_f64(engine, pages_vals):
     groups = []
     for i, vals in enumerate(pages_vals):
@@ -69,6 +84,9 @@ def test_chunked_decode_bit_exact(engine):
     cases.append(big)
     # all-constant page: maximal repeat-ctrl density, ~1 bit/value
     cases.append(np.full(60_000, 42.5))
+    # 64-bit windows and the two-step parse on both sides of sync points
+    cases.append(_alternating(2 * GOR_CHUNK + 1))
+    cases.append(_full_precision(3 * GOR_CHUNK + 7))
     gset = _upload_f64(engine, cases)
     out = torch.zeros(gset.rows, dtype=torch.float64, device="cuda")
     engine.decode(gset, 1, out)
@@ -248,6 +266,13 @@ def test_chunked_null_pages_bit_exact(engine):
     valid2 = np.zeros(n, dtype=bool)
     valid2[n // 2:] = True
     cases.append((vals, valid2))
+    # 64-bit windows and the two-step parse on both sides of sync points
+    nrng = np.random.default_rng(20251022)
+    for n in (GOR_CHUNK + 3, 3 * GOR_CHUNK + 7):
+        for vals in (_alternating(n), _full_precision(n)):
+            valid = nrng.random(n) > 0.10
+            valid[0] = True
+            cases.append((vals, valid))
     gset = _upload_f64_nulls(engine, cases)
     out = torch.zeros(gset.rows, dtype=torch.float64, device="cuda")
     dv = torch.zeros(gset.rows, dtype=torch.uint8, device="cuda")

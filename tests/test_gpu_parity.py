@@ -606,6 +606,28 @@ def test_truncated_gorilla_stream_errors(engine):
     gset.free()
 
 
+def test_short_gorilla_page_errors(engine):
+    """A Gorilla page too short to hold its header value (1..9 data bytes)
+    goes to the sequential kernel and must fail decode; with 10 bytes it
+    holds the header but no sentinel, and must fail through the chunked
+    kernels.  Both all-valid and with a null in the bitset."""
+    data = gs.encode_f64(np.array([1.5, 2.5, 3.5, 4.5]))
+    assert len(data) > 10
+    ts = np.arange(4, dtype=np.int64) * 1000
+    with_null = np.packbits(np.array([1, 1, 0, 1], dtype=bool),
+                            bitorder="little")
+    for cut in (1, 5, 9, 10):
+        for bitset in (None, with_null):
+            page = gs.build_page(data[:cut], 4, bitset)
+            gset = engine.upload([(0, [(gs.page_of(ts, gs.CT_TIME),
+                                        gs.CT_TIME),
+                                       (page, gs.CT_F64)])])
+            out = torch.zeros(gset.rows, dtype=torch.float64, device="cuda")
+            with pytest.raises(RuntimeError):
+                engine.decode(gset, 1, out)
+            gset.free()
+
+
 def test_scan_fused_agg_multigroup(engine):
     """Fused aggregate with several page-groups per series (merged into
     one series-group): per-group RLE deltas differ, groups are separated
