@@ -102,6 +102,9 @@ __device__ __forceinline__ bool dev_varint(const uint8_t *p, uint32_t len,
                            binary-search span/tombstone kernels; fail
                            loudly instead (the reference's row-wise
                            filtering cannot mis-select) */
+/* raised by k_encode_pages only, read by gs_encode_pages_dev */
+#define DERR_ENC_SENTINEL 8u /* Gorilla sentinel as an input value */
+#define DERR_ENC_NULL 16u    /* null row in a ts/i64 page */
 
 /* --------------------------------------------- pull-style value iterators */
 
@@ -3233,13 +3236,14 @@ __global__ void k_encode_pages(int kind /*0=ts 1=i64 2=f64*/,
                 bool av = true;
                 for (int32_t r = 0; r < ps.nrows; r++)
                     if (!valid[ps.row_off + r]) { av = false; break; }
-                if (!av) { atomicOr(err, DERR_FORMAT); lens[p] = -3; continue; }
+                if (!av) { atomicOr(err, DERR_ENC_NULL); lens[p] = -3; continue; }
             }
             dl = dev_enc_int((const int64_t *)vals, ps.row_off, ps.nrows,
                              data, kind == 0);
         }
         if (dl < 0) {
-            atomicOr(err, DERR_FORMAT);
+            /* -1: dev_enc_gorilla met the sentinel; -2: dev_enc_int */
+            atomicOr(err, dl == -1 ? DERR_ENC_SENTINEL : DERR_FORMAT);
             lens[p] = dl;
             continue;
         }
@@ -5021,7 +5025,20 @@ GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
     hipFree(d_specs);
     hipFree(d_lens);
     if (st != GS_OK) return st;
-    return check_dev_err(ctx);
+    /* the encoder's own error surface: pages that failed have a negative
+       h_lens entry, every other page of the launch is complete */
+    unsigned e = 0;
+    HIP_TRY(hipMemcpy(&e, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (!e) return GS_OK;
+    hipMemset(ctx->d_err, 0, sizeof(unsigned));
+    if (e & DERR_ENC_SENTINEL)
+        return fail(GS_ERR_SENTINEL,
+                    "encode: Gorilla sentinel value in the input");
+    if (e & DERR_ENC_NULL)
+        return fail(GS_ERR_FORMAT,
+                    "encode: null row in a ts/i64 page (integer pages must "
+                    "be all-valid)");
+    return fail(GS_ERR_FORMAT, "encode: value out of simple8b range");
 }
 
 /* Host-side setup shared by both merge entries: everything that depends

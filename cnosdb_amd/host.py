@@ -271,6 +271,12 @@ def str_page_of(strings, valid=None):
     return build_page(encode_str(present), nrows, bitset)
 
 
+def crc32(data):
+    """CRC-32/ISO-HDLC of a page's data region (tsm/page.rs:58-76)."""
+    d = np.frombuffer(bytes(data), dtype=np.uint8)
+    return int(PageLib().lib.gs_crc32(_np_ptr(d), ctypes.c_size_t(d.size)))
+
+
 def build_page(data, nrows, bitset=None):
     """Assemble full page bytes (tsm/page.rs layout). bitset: packed
     LSB-first validity bytes; None -> all valid."""
@@ -581,7 +587,9 @@ class Engine:
     def encode_pages_dev(self, kind, d_vals, row_off, rows, d_out,
                          cap_per_page, d_valid=None):
         """GPU page re-encode. kind: 0=ts 1=i64 2=f64. row_off/rows: host
-        numpy arrays; d_out capacity npages*cap_per_page. Returns lens."""
+        numpy arrays; d_out capacity npages*cap_per_page. Returns lens.
+        The exception of a failed call carries .status (GsStatus) and
+        .lens (negative where a page failed, see cnosdb_gs.h)."""
         row_off = np.ascontiguousarray(row_off, dtype=np.int64)
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         npages = row_off.size
@@ -592,7 +600,10 @@ class Engine:
             _np_ptr(row_off), _np_ptr(rows), npages,
             ctypes.c_void_p(d_out.data_ptr()), cap_per_page, _np_ptr(lens))
         if st != 0:
-            raise RuntimeError(f"gs_encode_pages_dev failed ({st}): {self._pl.err()}")
+            e = RuntimeError(
+                f"gs_encode_pages_dev failed ({st}): {self._pl.err()}")
+            e.status, e.lens = st, lens
+            raise e
         return lens
 
     def _mk_spec(self, d_ts, d_val, time_range, tombstones, d_out_ts,

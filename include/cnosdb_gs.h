@@ -305,7 +305,14 @@ GsStatus gs_scan_wait(GsCtx *ctx, GsGroupSet *set, GsScanResult *result);
  * page (header+crc+bitset+data, byte-exact with the host encoder) is
  * written at d_out + p*cap_per_page; h_lens receives encoded lengths.
  * Int encoders (kind 0/1) require all-valid slices — the time column is
- * never null; null-carrying i64 re-encode stays on the host encoder. */
+ * never null; null-carrying i64 re-encode stays on the host encoder.
+ *
+ * Errors: GS_ERR_CAP (before any device work) when cap_per_page is below
+ * the worst case for the longest page; GS_ERR_SENTINEL when an f64 page
+ * holds the Gorilla sentinel as a non-first value, as gs_encode_f64
+ * reports it; GS_ERR_FORMAT for a null row in a ts/i64 page.  On the last
+ * two h_lens is still filled: the pages that failed have a negative
+ * entry, every other page of the launch is complete and valid. */
 GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
                              const uint8_t *d_valid, const int64_t *h_row_off,
                              const int32_t *h_rows, int32_t npages,

@@ -151,12 +151,15 @@ def test_uncompressed_path_large_deltas():
 
 
 def test_simple8b_run_of_ones_selectors():
-    # simple8b.rs:28-48: 240/120 runs of 1 (via i64 with delta 1 is RLE;
-    # use non-monotone pattern to force simple8b with many 1-deltas)
-    base = np.arange(300, dtype=np.int64)
-    base[::7] += 3  # break RLE
+    # simple8b.rs:28-48: 240/120 runs of 1.  The packed value is the
+    # ZIGZAGGED delta, so the run is a delta of -1 (+1 zigzags to 2); a
+    # pure run would be RLE, so one other delta ends it: 360 ones pack as
+    # a selector-0 word (240) and a selector-1 word (120)
+    base = 1000 - np.arange(361, dtype=np.int64)
+    base = np.concatenate([base, [base[-1] + 7]])
     enc = orc.encode_i64(base)
     assert (enc[1] >> 4) == 1
+    assert [enc[i] >> 4 for i in range(10, len(enc), 8)] == [0, 1, 15]
     assert orc.decode_i64(enc, base.size).tolist() == base.tolist()
 
 
