@@ -3260,6 +3260,254 @@ __global__ void k_encode_pages(int kind /*0=ts 1=i64 2=f64*/,
     }
 }
 
+/* ---- column-group re-encode (gs_encode_group_pages_dev): every page of
+ * every column of a merged column group in two launches.  k_enc_prepare
+ * does the per-page work that parallelises (bitset, null densification,
+ * count, statistics, bool packing), one block per (column, page);
+ * k_enc_group_pages then runs the serial int/Gorilla encoders above over
+ * the dense values, one thread per (column, page), and seals the page. */
+
+struct EncGroupCol {
+    const void *vals;     /* 8 B/row; bool 1 B/row */
+    const uint8_t *valid; /* 1 B/row, NULL = all valid */
+    void *dense;          /* non-null values in row order at the page's
+                             row_off; NULL when valid is NULL (the source
+                             column is already dense) */
+    uint8_t *out;
+    int64_t cap;
+    int32_t ctype;
+    int32_t pad;
+};
+
+#define ENC_PREP_THREADS 256
+#define ENC_PREP_WAVES (ENC_PREP_THREADS / 64)
+
+/* a < b / a == b in the column's own type, on raw bits */
+__device__ __forceinline__ bool enc_lt(int ct, uint64_t a, uint64_t b) {
+    if (ct == GS_CT_F64)
+        return __longlong_as_double((long long)a) <
+               __longlong_as_double((long long)b);
+    if (ct == GS_CT_U64) return a < b;
+    return int64_t(a) < int64_t(b);
+}
+__device__ __forceinline__ bool enc_eq(int ct, uint64_t a, uint64_t b) {
+    if (ct == GS_CT_F64)
+        return __longlong_as_double((long long)a) ==
+               __longlong_as_double((long long)b);
+    return a == b;
+}
+/* Page statistics restate a sequential loop with strict compares
+ * (tsm/page.rs:137-290): of values that compare equal the FIRST in row
+ * order stays (this decides the sign of a zero extremum), and a NaN never
+ * compares, so it changes nothing.  (value, row) under "smaller value, then
+ * smaller row" is a total order over the non-NaN values, so the reduction
+ * below gives that loop's bits for any partition of the rows. */
+__device__ __forceinline__ void enc_min_merge(int ct, uint64_t &a, int32_t &ra,
+                                              uint64_t b, int32_t rb) {
+    if (enc_lt(ct, b, a) || (enc_eq(ct, b, a) && rb < ra)) { a = b; ra = rb; }
+}
+__device__ __forceinline__ void enc_max_merge(int ct, uint64_t &a, int32_t &ra,
+                                              uint64_t b, int32_t rb) {
+    if (enc_lt(ct, a, b) || (enc_eq(ct, b, a) && rb < ra)) { a = b; ra = rb; }
+}
+__device__ __forceinline__ int dev_varint_len(uint32_t v) {
+    return 1 + (v >= (1u << 7)) + (v >= (1u << 14)) + (v >= (1u << 21)) +
+           (v >= (1u << 28));
+}
+
+/* One block per (column, page), work item w = c*npages + p.  Each step
+ * takes ENC_PREP_THREADS rows: a wave's __ballot of the validity bytes is
+ * 8 bytes of the LSB-first bitset, written straight into the page by
+ * lanes 0..7; a valid row's slot in the dense column is the count of valid
+ * rows before it (earlier steps + earlier waves through LDS + __popcll of
+ * the ballot below the lane).  Validity is loaded by bytes only (see the
+ * hazard note in DESIGN.md).  Value slots of null rows are never read.
+ * Plain stores in a fixed order; nothing depends on the grid size. */
+__global__ __launch_bounds__(ENC_PREP_THREADS) void k_enc_prepare(
+    const EncGroupCol *__restrict__ cols, int ncols,
+    const EncPageSpec *__restrict__ pages, int npages,
+    int32_t *__restrict__ cnt, GsPageInfo *__restrict__ info) {
+    __shared__ int32_t wcnt[ENC_PREP_WAVES];
+    __shared__ uint64_t smin[ENC_PREP_WAVES], smax[ENC_PREP_WAVES];
+    __shared__ int32_t sminr[ENC_PREP_WAVES], smaxr[ENC_PREP_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nwork = ncols * npages;
+    for (int w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int c = w / npages, p = w - c * npages;
+        const EncGroupCol col = cols[c];
+        const EncPageSpec ps = pages[p];
+        const int ct = col.ctype;
+        const bool is_bool = ct == GS_CT_BOOL;
+        const int32_t n = ps.nrows;
+        const int32_t bl = (n + 7) / 8;
+        uint8_t *bs = col.out + int64_t(p) * col.cap + 16;
+        const uint8_t *vd = col.valid ? col.valid + ps.row_off : nullptr;
+        const uint64_t *v8 = (const uint64_t *)col.vals + ps.row_off;
+        const uint8_t *v1 = (const uint8_t *)col.vals + ps.row_off;
+
+        uint64_t mn, mx;
+        if (ct == GS_CT_F64) {
+            mn = 0x7FEFFFFFFFFFFFFFULL; /* DBL_MAX */
+            mx = 0xFFEFFFFFFFFFFFFFULL; /* -DBL_MAX */
+        } else if (ct == GS_CT_U64) {
+            mn = ~0ULL;
+            mx = 0;
+        } else {
+            mn = 0x7FFFFFFFFFFFFFFFULL; /* INT64_MAX */
+            mx = 0x8000000000000000ULL; /* INT64_MIN */
+        }
+        int32_t mnr = INT32_MAX, mxr = INT32_MAX;
+
+        int32_t carry = 0; /* valid rows before this step */
+        for (int32_t base = 0; base < n; base += ENC_PREP_THREADS) {
+            const int32_t r = base + int32_t(threadIdx.x);
+            const bool v = r < n && (!vd || vd[r] != 0);
+            const uint64_t b = __ballot(v);
+            if (lane < 8) {
+                int32_t bi = (base >> 3) + wave * 8 + lane;
+                if (bi < bl) bs[bi] = uint8_t(b >> (8 * lane));
+            }
+            uint64_t x = 0;
+            if (v && !is_bool) x = v8[r];
+            if (v && is_bool && vd) x = v1[r];
+            if (v && !is_bool) {
+                enc_min_merge(ct, mn, mnr, x, r);
+                enc_max_merge(ct, mx, mxr, x, r);
+            }
+            if (vd) { /* same for the whole block */
+                if (lane == 0) wcnt[wave] = __popcll(b);
+                __syncthreads();
+                int32_t pos = carry, tot = 0;
+                for (int k = 0; k < ENC_PREP_WAVES; k++) {
+                    if (k < wave) pos += wcnt[k];
+                    tot += wcnt[k];
+                }
+                pos += __popcll(b & ((1ULL << lane) - 1));
+                if (v) {
+                    if (is_bool)
+                        ((uint8_t *)col.dense)[ps.row_off + pos] = uint8_t(x);
+                    else
+                        ((uint64_t *)col.dense)[ps.row_off + pos] = x;
+                }
+                carry += tot;
+                __syncthreads(); /* wcnt is rewritten by the next step */
+            }
+        }
+        const int32_t nn = vd ? carry : n; /* non-null rows */
+
+        if (!is_bool) {
+            for (int o = 32; o > 0; o >>= 1) {
+                uint64_t ob = __shfl_xor(mn, o);
+                int32_t orow = __shfl_xor(mnr, o);
+                enc_min_merge(ct, mn, mnr, ob, orow);
+                ob = __shfl_xor(mx, o);
+                orow = __shfl_xor(mxr, o);
+                enc_max_merge(ct, mx, mxr, ob, orow);
+            }
+            if (lane == 0) {
+                smin[wave] = mn; sminr[wave] = mnr;
+                smax[wave] = mx; smaxr[wave] = mxr;
+            }
+        }
+        __syncthreads(); /* also: this block's dense stores are visible */
+        if (threadIdx.x == 0) {
+            if (is_bool) {
+                mn = mx = 0;
+            } else {
+                for (int k = 1; k < ENC_PREP_WAVES; k++) {
+                    enc_min_merge(ct, mn, mnr, smin[k], sminr[k]);
+                    enc_max_merge(ct, mx, mxr, smax[k], smaxr[k]);
+                }
+            }
+            cnt[w] = nn;
+            info[w].null_count = int64_t(n) - nn;
+            info[w].min_bits = mn;
+            info[w].max_bits = mx;
+        }
+        if (is_bool && nn > 0) {
+            /* bool_bitpack_encode (boolean.rs:24-64): [10][1<<4][varint n]
+               then the values MSB-first from a byte boundary; one output
+               byte per thread from 8 dense bytes */
+            const uint8_t *src = vd ? (const uint8_t *)col.dense + ps.row_off : v1;
+            uint8_t *data = bs + bl;
+            const int vi = dev_varint_len(uint32_t(nn));
+            if (threadIdx.x == 0) {
+                data[0] = GS_ENC_BITPACK;
+                data[1] = 1 << 4;
+                dev_varint_put(data + 2, uint64_t(nn));
+            }
+            const int32_t nb = (nn + 7) / 8;
+            for (int32_t j = threadIdx.x; j < nb; j += ENC_PREP_THREADS) {
+                uint8_t byte = 0;
+                for (int k = 0; k < 8; k++) {
+                    int32_t i = j * 8 + k;
+                    if (i < nn && src[i]) byte |= uint8_t(0x80u >> k);
+                }
+                data[2 + vi + j] = byte;
+            }
+        }
+        __syncthreads(); /* smin.. are rewritten by the next work item */
+    }
+}
+
+/* one thread per (column, page): encode the dense values, then crc and
+ * header as in k_encode_pages */
+__global__ void k_enc_group_pages(const EncGroupCol *__restrict__ cols,
+                                  int ncols,
+                                  const EncPageSpec *__restrict__ pages,
+                                  int npages, const int32_t *__restrict__ cnt,
+                                  GsPageInfo *__restrict__ info,
+                                  unsigned *__restrict__ err) {
+    __shared__ uint32_t crct[256];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+        crct[i] = c;
+    }
+    __syncthreads();
+    const int nwork = ncols * npages;
+    for (int w = blockIdx.x * blockDim.x + threadIdx.x; w < nwork;
+         w += gridDim.x * blockDim.x) {
+        const int c = w / npages, p = w - c * npages;
+        const EncGroupCol col = cols[c];
+        const EncPageSpec ps = pages[p];
+        uint8_t *pg = col.out + int64_t(p) * col.cap;
+        const uint32_t bl = uint32_t(ps.nrows + 7) / 8;
+        uint8_t *data = pg + 16 + bl;
+        const int32_t nn = cnt[w];
+        if (col.ctype == GS_CT_TIME && nn != ps.nrows) {
+            atomicOr(err, DERR_ENC_NULL); /* the time column is never null */
+            info[w].len = -3;
+            continue;
+        }
+        const void *src = col.dense ? col.dense : col.vals;
+        int64_t dl;
+        if (col.ctype == GS_CT_F64)
+            dl = dev_enc_gorilla((const double *)src, nullptr, ps.row_off, nn,
+                                 data);
+        else if (col.ctype == GS_CT_BOOL) /* packed by k_enc_prepare */
+            dl = nn ? 2 + dev_varint_len(uint32_t(nn)) + (nn + 7) / 8 : 0;
+        else /* u64 is the i64 codec over the same bits (unsigned.rs:15-18) */
+            dl = dev_enc_int((const int64_t *)src, ps.row_off, nn, data,
+                             col.ctype == GS_CT_TIME);
+        if (dl < 0) {
+            atomicOr(err, dl == -1 ? DERR_ENC_SENTINEL : DERR_FORMAT);
+            info[w].len = dl;
+            continue;
+        }
+        uint32_t crc = 0xFFFFFFFFu;
+        for (int64_t i = 0; i < dl; i++)
+            crc = crct[(crc ^ data[i]) & 0xFF] ^ (crc >> 8);
+        crc ^= 0xFFFFFFFFu;
+        pg[0] = uint8_t(bl >> 24); pg[1] = uint8_t(bl >> 16);
+        pg[2] = uint8_t(bl >> 8); pg[3] = uint8_t(bl);
+        dev_put_be64(pg + 4, uint64_t(ps.nrows));
+        pg[12] = uint8_t(crc >> 24); pg[13] = uint8_t(crc >> 16);
+        pg[14] = uint8_t(crc >> 8); pg[15] = uint8_t(crc);
+        info[w].len = 16 + int64_t(bl) + dl;
+    }
+}
+
 /* ------------------------------------------------------------- host state */
 
 struct GsCtx {
@@ -5038,6 +5286,131 @@ GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
         return fail(GS_ERR_FORMAT,
                     "encode: null row in a ts/i64 page (integer pages must "
                     "be all-valid)");
+    return fail(GS_ERR_FORMAT, "encode: value out of simple8b range");
+}
+
+GsStatus gs_encode_group_pages_dev(GsCtx *ctx, int32_t ncols,
+                                   const uint8_t *ctype,
+                                   const void *const *d_vals,
+                                   const uint8_t *const *d_valid,
+                                   const int64_t *h_row_off,
+                                   const int32_t *h_rows, int32_t npages,
+                                   uint8_t *const *d_out,
+                                   const int64_t *cap_per_page,
+                                   GsPageInfo *h_info) {
+    if (ncols < 1 || ncols > GS_MAX_ENCODE_COLS)
+        return fail(GS_ERR, "gs_encode_group_pages_dev: ncols outside "
+                            "1..GS_MAX_ENCODE_COLS");
+    if (!ctx || !ctype || !d_vals || !h_row_off || !h_rows || !d_out ||
+        !cap_per_page || !h_info)
+        return fail(GS_ERR, "gs_encode_group_pages_dev: NULL argument");
+    if (npages <= 0)
+        return fail(GS_ERR, "gs_encode_group_pages_dev: npages <= 0");
+    if (int64_t(ncols) * npages > INT32_MAX)
+        return fail(GS_ERR, "gs_encode_group_pages_dev: too many pages");
+    int64_t maxr = 0, extent = 0;
+    for (int32_t p = 0; p < npages; p++) {
+        if (h_rows[p] < 0 || h_row_off[p] < 0)
+            return fail(GS_ERR, "gs_encode_group_pages_dev: negative page "
+                                "offset or row count");
+        if (h_rows[p] > maxr) maxr = h_rows[p];
+        if (h_row_off[p] + h_rows[p] > extent) extent = h_row_off[p] + h_rows[p];
+    }
+    for (int32_t c = 0; c < ncols; c++) {
+        if (ctype[c] != GS_CT_TIME && ctype[c] != GS_CT_I64 &&
+            ctype[c] != GS_CT_F64 && ctype[c] != GS_CT_BOOL &&
+            ctype[c] != GS_CT_U64)
+            return fail(GS_ERR, "gs_encode_group_pages_dev: column type must "
+                                "be time, i64, f64, bool or u64 (strings use "
+                                "gs_encode_str)");
+        if (!d_vals[c] || !d_out[c])
+            return fail(GS_ERR, "gs_encode_group_pages_dev: NULL column "
+                                "buffer");
+    }
+    for (int32_t c = 0; c < ncols; c++) {
+        /* worst case: ints -> uncompressed 8 B/val; f64 -> ~77 bits/val;
+           bool -> header, 10-byte varint bound and one bit per value */
+        int64_t need = 16 + (maxr + 7) / 8;
+        if (ctype[c] == GS_CT_F64) need += 2 + 8 + (maxr + 1) * 10 + 16;
+        else if (ctype[c] == GS_CT_BOOL) need += 2 + 10 + (maxr + 7) / 8;
+        else need += 2 + 8 * maxr + 32;
+        if (cap_per_page[c] < need)
+            return fail(GS_ERR_CAP, "gs_encode_group_pages_dev: cap_per_page "
+                                    "below worst-case encoded size");
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t nwork = size_t(ncols) * size_t(npages);
+    std::vector<void *> scratch;
+    auto release = [&]() { for (void *q : scratch) hipFree(q); };
+    auto dalloc = [&](size_t bytes) -> void * {
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) return nullptr;
+        scratch.push_back(q);
+        return q;
+    };
+    std::vector<EncGroupCol> cols(ncols);
+    for (int32_t c = 0; c < ncols; c++) {
+        cols[c].vals = d_vals[c];
+        cols[c].valid = d_valid ? d_valid[c] : nullptr;
+        cols[c].dense = nullptr;
+        cols[c].out = d_out[c];
+        cols[c].cap = cap_per_page[c];
+        cols[c].ctype = ctype[c];
+        cols[c].pad = 0;
+        if (cols[c].valid) { /* only null-carrying columns are densified */
+            cols[c].dense =
+                dalloc(size_t(extent) * (ctype[c] == GS_CT_BOOL ? 1 : 8));
+            if (!cols[c].dense) {
+                release();
+                return fail(GS_ERR, "hipMalloc dense scratch failed");
+            }
+        }
+    }
+    std::vector<EncPageSpec> specs(npages);
+    for (int32_t p = 0; p < npages; p++) {
+        specs[p].row_off = h_row_off[p];
+        specs[p].nrows = h_rows[p];
+        specs[p].pad = 0;
+    }
+    EncGroupCol *d_cols = (EncGroupCol *)dalloc(cols.size() * sizeof(EncGroupCol));
+    EncPageSpec *d_specs = (EncPageSpec *)dalloc(specs.size() * sizeof(EncPageSpec));
+    int32_t *d_cnt = (int32_t *)dalloc(nwork * sizeof(int32_t));
+    GsPageInfo *d_info = (GsPageInfo *)dalloc(nwork * sizeof(GsPageInfo));
+    if (!d_cols || !d_specs || !d_cnt || !d_info) {
+        release();
+        return fail(GS_ERR, "hipMalloc encode tables failed");
+    }
+    hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(EncGroupCol),
+                   hipMemcpyHostToDevice, ctx->stream);
+    hipMemcpyAsync(d_specs, specs.data(), specs.size() * sizeof(EncPageSpec),
+                   hipMemcpyHostToDevice, ctx->stream);
+    hipLaunchKernelGGL(k_enc_prepare, dim3(grid_for(int(nwork), 1)),
+                       dim3(ENC_PREP_THREADS), 0, ctx->stream, d_cols, ncols,
+                       d_specs, npages, d_cnt, d_info);
+    /* thread per page: 64-thread blocks spread the serial encoders over
+       more CUs than 256-thread blocks would */
+    hipLaunchKernelGGL(k_enc_group_pages, dim3(grid_for(int(nwork), 64)),
+                       dim3(64), 0, ctx->stream, d_cols, ncols, d_specs,
+                       npages, d_cnt, d_info, ctx->d_err);
+    GsStatus st = GS_OK;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess)
+        st = fail(GS_ERR, "group encode kernels failed");
+    else if (hipMemcpy(h_info, d_info, nwork * sizeof(GsPageInfo),
+                       hipMemcpyDeviceToHost) != hipSuccess)
+        st = fail(GS_ERR, "group encode: page info readback failed");
+    release();
+    if (st != GS_OK) return st;
+    /* same error surface as gs_encode_pages_dev: failed cells have a
+       negative len, every other cell of the launch is complete */
+    unsigned e = 0;
+    HIP_TRY(hipMemcpy(&e, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (!e) return GS_OK;
+    hipMemset(ctx->d_err, 0, sizeof(unsigned));
+    if (e & DERR_ENC_SENTINEL)
+        return fail(GS_ERR_SENTINEL,
+                    "encode: Gorilla sentinel value in the input");
+    if (e & DERR_ENC_NULL)
+        return fail(GS_ERR_FORMAT, "encode: null row in the time column");
     return fail(GS_ERR_FORMAT, "encode: value out of simple8b range");
 }
 

@@ -98,6 +98,17 @@ class GsScanResult(ctypes.Structure):
     ]
 
 
+# GsPageInfo as numpy sees it; min/max are re-viewed per column type
+_PAGE_INFO_DT = np.dtype([("len", "<i8"), ("null_count", "<i8"),
+                          ("min", "<u8"), ("max", "<u8")])
+
+
+def _page_info_dtype(ctype):
+    t = {CT_TIME: "<i8", CT_I64: "<i8", CT_F64: "<f8"}.get(int(ctype), "<u8")
+    return np.dtype([("len", "<i8"), ("null_count", "<i8"),
+                     ("min", t), ("max", t)])
+
+
 class PageLib:
     """Loads libcnosdb_gs.so and declares signatures. Singleton per process."""
 
@@ -171,6 +182,12 @@ class PageLib:
             ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
             ctypes.c_int64, ctypes.c_void_p]
+        lib.gs_encode_group_pages_dev.restype = ctypes.c_int32
+        lib.gs_encode_group_pages_dev.argtypes = [
+            ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+            ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p]
         lib.gs_export_group_column.restype = ctypes.c_int32
         lib.gs_export_group_column.argtypes = [
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -317,6 +334,10 @@ def page_of(values, ctype, valid=None):
         data = encode_f64(present.astype(np.float64))
     elif ctype == CT_BOOL:
         data = encode_bool(present.astype(np.uint8))
+    elif ctype == CT_U64:
+        # u64 is the i64 codec over the bit-cast values (unsigned.rs:15-18)
+        data = encode_i64(
+            np.ascontiguousarray(present).astype(np.uint64).view(np.int64))
     else:
         raise ValueError(ctype)
     return build_page(data, nrows, bitset)
@@ -606,6 +627,48 @@ class Engine:
             raise e
         return lens
 
+    def encode_group_pages_dev(self, cols, row_off, rows, outs):
+        """GPU re-encode of a whole column group (gs_encode_group_pages_dev),
+        taking compact_merge_fields' outputs as they are.  cols =
+        [(ctype, d_vals, d_valid_or_None), ...] with the time column among
+        them; row_off/rows: the page split shared by all columns; outs =
+        [(d_out, cap_per_page), ...], page p of column c at
+        d_out[p*cap:].  Returns one structured array per column with
+        fields len, null_count, min, max ([npages]; min/max in the
+        column's dtype, 0 for bool).  The exception of a failed call
+        carries .status (GsStatus) and .info (the same list; len < 0
+        exactly where a page failed, see cnosdb_gs.h)."""
+        if len(cols) != len(outs):
+            raise ValueError(f"{len(cols)} columns, {len(outs)} outputs")
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        npages, ncols = row_off.size, len(cols)
+        if rows.size != npages:
+            raise ValueError("row_off and rows differ in length")
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        ct = np.array([c[0] for c in cols], dtype=np.uint8)
+        val_p = (ctypes.c_void_p * max(ncols, 1))(*[ptr(c[1]) for c in cols])
+        vd_p = None  # whole array NULL: every column all-valid
+        if any(c[2] is not None for c in cols):
+            vd_p = (ctypes.c_void_p * ncols)(*[ptr(c[2]) for c in cols])
+        out_p = (ctypes.c_void_p * max(ncols, 1))(*[ptr(o[0]) for o in outs])
+        caps = np.array([o[1] for o in outs], dtype=np.int64)
+        raw = np.zeros(max(ncols, 1) * max(npages, 1), dtype=_PAGE_INFO_DT)
+        st = self.lib.gs_encode_group_pages_dev(
+            self._ctx, ncols, _np_ptr(ct), val_p, vd_p, _np_ptr(row_off),
+            _np_ptr(rows), npages, out_p, _np_ptr(caps), _np_ptr(raw))
+        info = [raw[c * npages:(c + 1) * npages].view(_page_info_dtype(ct[c]))
+                for c in range(ncols)]
+        if st != 0:
+            e = RuntimeError(
+                f"gs_encode_group_pages_dev failed ({st}): {self._pl.err()}")
+            e.status, e.info = st, info
+            raise e
+        return info
+
     def _mk_spec(self, d_ts, d_val, time_range, tombstones, d_out_ts,
                  d_out_val, agg, field_col=0):
         spec = GsScanSpec()
@@ -734,6 +797,36 @@ def prune_column_groups(stats, time_range=None, value_pred=None):
                 k = max_v >= a and min_v <= b
         keep.append(bool(k))
     return keep
+
+
+def fold_page_stats(ts_info, val_info=None, page_ranges=None):
+    """Fold the page statistics Engine.encode_group_pages_dev returns into
+    the (min_ts, max_ts, min_val, max_val) tuples prune_column_groups
+    takes.  ts_info / val_info: one series' per-page records of the time
+    column and of one field column (val_info None -> no value stats).
+    page_ranges: [(p0, p1), ...] half-open page ranges to fold into one
+    tuple each; None -> one tuple per page (a page is one column group).
+
+    A page without a non-null value reports the starting values of the
+    reference's loop (min > max), and so does an f64 page that holds only
+    NaNs; such a page contributes nothing, and a range without any
+    contributing page gets min_val = max_val = None (never prunable)."""
+    npages = len(ts_info)
+    if page_ranges is None:
+        page_ranges = [(p, p + 1) for p in range(npages)]
+    out = []
+    for p0, p1 in page_ranges:
+        t = ts_info[p0:p1]
+        min_ts = t["min"].min() if len(t) else np.iinfo(np.int64).max
+        max_ts = t["max"].max() if len(t) else np.iinfo(np.int64).min
+        min_v = max_v = None
+        if val_info is not None:
+            v = val_info[p0:p1]
+            v = v[v["min"] <= v["max"]]
+            if len(v):
+                min_v, max_v = v["min"].min().item(), v["max"].max().item()
+        out.append((int(min_ts), int(max_ts), min_v, max_v))
+    return out
 
 
 def _bind_groupby(lib):

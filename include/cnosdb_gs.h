@@ -305,7 +305,9 @@ GsStatus gs_scan_wait(GsCtx *ctx, GsGroupSet *set, GsScanResult *result);
  * page (header+crc+bitset+data, byte-exact with the host encoder) is
  * written at d_out + p*cap_per_page; h_lens receives encoded lengths.
  * Int encoders (kind 0/1) require all-valid slices — the time column is
- * never null; null-carrying i64 re-encode stays on the host encoder.
+ * never null.  Null-carrying i64, u64 and bool columns, and the page
+ * statistics, are gs_encode_group_pages_dev's (below), which encodes a
+ * whole column group in one call.
  *
  * Errors: GS_ERR_CAP (before any device work) when cap_per_page is below
  * the worst case for the longest page; GS_ERR_SENTINEL when an f64 page
@@ -318,6 +320,57 @@ GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
                              const int32_t *h_rows, int32_t npages,
                              uint8_t *d_out, int64_t cap_per_page,
                              int64_t *h_lens);
+
+/* ---- GPU re-encode of a whole column group (the write side that follows
+ * gs_compact_merge_fields) ----
+ * Takes the merged columns as that call leaves them — the time column plus
+ * up to GS_MAX_MERGE_COLS i64/u64/f64/bool field columns, validity bytes
+ * and all — and writes every page of every column, each byte-exact with
+ * the host path (gs_encode_* over the non-null values + gs_build_page).
+ * The page split h_row_off/h_rows is shared by all columns.  u64 is the
+ * i64 codec over the same bits (codec/unsigned.rs:15-18); an all-null or
+ * zero-row page has an empty data region.  Value slots of null rows are
+ * never read: they may hold anything, the Gorilla sentinel included.
+ *
+ * h_info[c*npages + p] also receives the page's PageStatistics as
+ * Page::arrow_array_to_page computes them (tsm/page.rs:137-290): a
+ * sequential loop over the non-null values with strict compares, starting
+ * from INT64_MAX/INT64_MIN (time, i64), UINT64_MAX/0 (u64) or
+ * DBL_MAX/-DBL_MAX (f64).  So a NaN changes neither bound, of +0.0 and
+ * -0.0 the extremum keeps the sign of the first in row order, and a page
+ * without a non-null value reports the starting values.  bool has no
+ * min/max (0).  The bits do not depend on the launch geometry.
+ *
+ * GS_ERR (with a message, before any device work) for ncols outside
+ * 1..GS_MAX_ENCODE_COLS, a ctype other than the five above (strings stay
+ * with gs_encode_str), npages <= 0 or a NULL required pointer;
+ * GS_ERR_CAP when a cap_per_page[c] is below that column's worst case for
+ * the longest page (ints and f64 as in gs_encode_pages_dev, bool
+ * 16 + ceil(n/8) + 2 + 10 + ceil(n/8)).  After the launch:
+ * GS_ERR_SENTINEL for a non-first non-null f64 equal to the Gorilla
+ * sentinel, GS_ERR_FORMAT for a null row in a GS_CT_TIME column, ranked
+ * as in gs_encode_pages_dev.  h_info is then still filled: exactly the
+ * failed (column, page) cells have len < 0, every other cell is complete
+ * and valid. */
+#define GS_MAX_ENCODE_COLS 33 /* time + GS_MAX_MERGE_COLS fields */
+
+typedef struct {
+    int64_t len;        /* full page length; negative = this page failed */
+    int64_t null_count; /* rows - non-null rows */
+    uint64_t min_bits;  /* raw bits in the column's type; 0 for bool */
+    uint64_t max_bits;
+} GsPageInfo;
+
+GsStatus gs_encode_group_pages_dev(
+    GsCtx *ctx, int32_t ncols,
+    const uint8_t *ctype,          /* [ncols] GS_CT_TIME/I64/F64/BOOL/U64 */
+    const void *const *d_vals,     /* [ncols] 8 B/row; bool 1 B/row (gs_decode widths) */
+    const uint8_t *const *d_valid, /* [ncols] 1 B/row; entry or array NULL = all valid */
+    const int64_t *h_row_off, const int32_t *h_rows, int32_t npages,
+    uint8_t *const *d_out,         /* [ncols]; page p of column c at
+                                      d_out[c] + p*cap_per_page[c] */
+    const int64_t *cap_per_page,   /* [ncols] */
+    GsPageInfo *h_info);           /* [ncols*npages], index c*npages + p */
 
 /* ---- compaction merge (BASELINE config #5) ----
  * k overlapping L0 column-group streams per series -> one merged, deduped
