@@ -1,290 +1,69 @@
-/* Host-side write path of the cnosdb_gs engine: the TSM DataBlock encoders
- * and page assembly.  This is the product's mirror of the reference's
- * encode side (tskv/src/tsm/codec/{timestamp,integer,simple8b,float,
- * boolean}.rs encode fns and Page::arrow_array_to_page, tsm/page.rs:
- * 100-353,488-497); byte-exact with the reference encoder, pinned by the
- * InfluxDB golden blocks (integer.rs:438-483) and the boolean vectors
- * (boolean.rs:156-181).  Used by the GPU read path's fixture/flush side;
- * runs on host CPU exactly as the reference writer does.
+/* Host-side write path of the cnosdb_gs engine: the C entry points of the
+ * TSM DataBlock encoders and of page assembly (the reference's
+ * Page::arrow_array_to_page, tsm/page.rs:100-353,488-497), plus the string
+ * block encoder.  The ts/i64/f64/bool codecs, the CRC and the page header
+ * are the functions of gs_tsm_enc.h, the same ones the device kernels run;
+ * this file checks capacities and maps their errors to the public codes.
+ * Used by the GPU read path's fixture/flush side; runs on host CPU exactly
+ * as the reference writer does.  Bytes of dst behind the returned length
+ * are unspecified.
  */
-#include "gs_internal.h"
+#include "gs_tsm_enc.h"
 #include <cstring>
+#include <memory>
 #include <vector>
 
 namespace {
 
-enum {
-    ENC_NULL = 1,
-    ENC_DELTA = 2,
-    ENC_GORILLA = 6,
-    ENC_BITPACK = 10,
-    ENC_DELTATS = 11,
-};
-enum { SUB_UNCOMPRESSED = 0, SUB_SIMPLE8B = 1, SUB_RLE = 2 };
-
-constexpr uint64_t S8B_MAX = (1ULL << 60) - 1;
-constexpr uint64_t SENTINEL = 0x7ff8000000000ffULL; /* float.rs:16 */
-
-inline void put_be64(uint8_t *p, uint64_t v) {
-    for (int i = 7; i >= 0; i--) { p[i] = uint8_t(v); v >>= 8; }
-}
-inline uint64_t zz(int64_t v) { return (uint64_t(v) << 1) ^ uint64_t(v >> 63); }
-
-size_t varint_put(uint8_t *dst, uint64_t v) {
-    size_t n = 0;
-    while (v >= 0x80) { dst[n++] = uint8_t(v | 0x80); v >>= 7; }
-    dst[n++] = uint8_t(v);
-    return n;
+/* TsmEncErr -> what gs_encode_* have always returned */
+int64_t host_code(int64_t r) {
+    if (r == TSM_ENC_ERR_SENTINEL) return GS_ERR_SENTINEL;
+    if (r == TSM_ENC_ERR_RANGE) return -1; /* value out of simple8b range */
+    return r;
 }
 
-/* simple8b greedy packer, simple8b.rs:26-76 */
-const uint8_t NUM_BITS[14][2] = {
-    {60, 1}, {30, 2}, {20, 3}, {15, 4}, {12, 5}, {10, 6}, {8, 7},
-    {7, 8},  {6, 10}, {5, 12}, {4, 15}, {3, 20}, {2, 30}, {1, 60},
-};
-
-int64_t s8b_encode(const uint64_t *src, size_t n, uint8_t *dst, size_t cap) {
-    size_t i = 0, w = 0;
-    while (i < n) {
-        size_t remain = n - i;
-        if (remain >= 120) {
-            size_t lim = remain >= 240 ? 240 : 120;
-            size_t k = 0;
-            while (k < lim && src[i + k] == 1) k++;
-            if (k == 240) {
-                if (w + 8 > cap) return -5;
-                memset(dst + w, 0, 8); w += 8; i += 240; continue;
-            }
-            if (k >= 120) {
-                if (w + 8 > cap) return -5;
-                put_be64(dst + w, 1ULL << 60); w += 8; i += 120; continue;
-            }
-        }
-        bool packed = false;
-        for (int idx = 0; idx < 14; idx++) {
-            size_t int_n = NUM_BITS[idx][0];
-            unsigned bit_n = NUM_BITS[idx][1];
-            if (int_n > remain) continue;
-            uint64_t max_val = 1ULL << (bit_n & 0x3f);
-            uint64_t word = (uint64_t(idx) + 2) << 60;
-            bool fits = true;
-            for (size_t k = 0; k < int_n; k++) {
-                if (src[i + k] >= max_val) { fits = false; break; }
-                word |= src[i + k] << ((k * bit_n) & 0x3f);
-            }
-            if (!fits) continue;
-            if (w + 8 > cap) return -5;
-            put_be64(dst + w, word); w += 8; i += int_n;
-            packed = true;
-            break;
-        }
-        if (!packed) return -1; /* value out of bounds */
-    }
-    return int64_t(w);
+int64_t encode_int(bool is_ts, const int64_t *src, size_t n, uint8_t *dst,
+                   size_t cap) {
+    if (n == 0) return 0;
+    if (cap < tsm_int_max_len(n)) return GS_ERR_CAP;
+    /* the packed values once, for the packer to look at more than once */
+    std::unique_ptr<uint64_t[]> scratch(new uint64_t[n]);
+    return host_code(tsm_enc_int(is_ts, src, n, dst, scratch.get()));
 }
 
 } // namespace
 
 extern "C" {
 
-/* ts_zigzag_simple8b_encode, timestamp.rs:51-122 (raw wrapping deltas, no
- * zigzag; RLE count includes the first value; divisor scaling in the
- * simple8b/RLE sub-paths; single-value blocks carry scaler nibble 12) */
 int64_t gs_encode_ts(const int64_t *src, size_t n, uint8_t *dst, size_t cap) {
-    if (n == 0) return 0;
-    if (cap < 2 + 8 * n + 16) return -5;
-    size_t w = 0;
-    dst[w++] = ENC_DELTATS;
-    std::vector<uint64_t> d(n);
-    for (size_t i = 0; i < n; i++) d[i] = uint64_t(src[i]);
-    uint64_t max = 0;
-    if (n > 1) {
-        for (size_t i = n - 1; i >= 1; i--) {
-            d[i] -= d[i - 1];
-            if (d[i] > max) max = d[i];
-            if (i == 1) break;
-        }
-        bool use_rle = true;
-        for (size_t i = 2; i < n; i++)
-            if (d[1] != d[i]) { use_rle = false; break; }
-        if (use_rle) {
-            dst[w++] = 0;
-            put_be64(dst + w, d[0]); w += 8;
-            uint64_t div = 1000000000000ULL;
-            while (div > 1 && d[1] % div != 0) div /= 10;
-            if (div > 1) {
-                unsigned sc = 0;
-                for (uint64_t x = div; x > 1; x /= 10) sc++;
-                dst[1] |= uint8_t(sc);
-                w += varint_put(dst + w, d[1] / div);
-            } else {
-                w += varint_put(dst + w, d[1]);
-            }
-            w += varint_put(dst + w, uint64_t(n));
-            dst[1] |= uint8_t(SUB_RLE << 4);
-            return int64_t(w);
-        }
-    }
-    if (max > S8B_MAX) {
-        dst[w++] = uint8_t(SUB_UNCOMPRESSED << 4);
-        for (size_t i = 0; i < n; i++) { put_be64(dst + w, d[i]); w += 8; }
-        return int64_t(w);
-    }
-    uint64_t div = 1000000000000ULL;
-    for (size_t i = 1; i < n && div > 1; i++)
-        while (div > 1 && d[i] % div != 0) div /= 10;
-    if (div > 1)
-        for (size_t i = 1; i < n; i++) d[i] /= div;
-    unsigned sc = 0;
-    for (uint64_t x = div; x > 1; x /= 10) sc++;
-    dst[w++] = uint8_t((SUB_SIMPLE8B << 4) | sc);
-    put_be64(dst + w, d[0]); w += 8;
-    int64_t s = s8b_encode(d.data() + 1, n - 1, dst + w, cap - w);
-    if (s < 0) return s;
-    return int64_t(w + size_t(s));
+    return encode_int(true, src, n, dst, cap);
 }
 
-/* i64_zigzag_simple8b_encode, integer.rs:40-96 (zigzag deltas; RLE needs
- * n>=3 and its count excludes the first value; no divisor) */
 int64_t gs_encode_i64(const int64_t *src, size_t n, uint8_t *dst, size_t cap) {
-    if (n == 0) return 0;
-    if (cap < 2 + 8 * n + 16) return -5;
-    size_t w = 0;
-    dst[w++] = ENC_DELTA;
-    std::vector<uint64_t> d(n);
-    for (size_t i = 0; i < n; i++) d[i] = uint64_t(src[i]);
-    uint64_t max = 0;
-    for (size_t i = n - 1; i >= 1; i--) {
-        d[i] = zz(int64_t(d[i] - d[i - 1]));
-        if (d[i] > max) max = d[i];
-        if (i == 1) break;
-    }
-    d[0] = zz(src[0]);
-    if (n > 2) {
-        bool use_rle = true;
-        for (size_t i = 2; i < n; i++)
-            if (d[1] != d[i]) { use_rle = false; break; }
-        if (use_rle) {
-            dst[w++] = 0;
-            put_be64(dst + w, d[0]); w += 8;
-            w += varint_put(dst + w, d[1]);
-            w += varint_put(dst + w, uint64_t(n) - 1);
-            dst[1] |= uint8_t(SUB_RLE << 4);
-            return int64_t(w);
-        }
-    }
-    if (max > S8B_MAX) {
-        dst[w++] = uint8_t(SUB_UNCOMPRESSED << 4);
-        for (size_t i = 0; i < n; i++) { put_be64(dst + w, d[i]); w += 8; }
-        return int64_t(w);
-    }
-    dst[w++] = uint8_t(SUB_SIMPLE8B << 4);
-    put_be64(dst + w, d[0]); w += 8;
-    int64_t s = s8b_encode(d.data() + 1, n - 1, dst + w, cap - w);
-    if (s < 0) return s;
-    return int64_t(w + size_t(s));
+    return encode_int(false, src, n, dst, cap);
 }
 
-/* f64_gorilla_encode, float.rs:32-243: XOR bitstream, MSB-first; leading
- * capped at 31 before the window comparison; meaningful 64 encoded as 0;
- * encoded NaN sentinel appended as terminator */
 int64_t gs_encode_f64(const double *src, size_t n, uint8_t *dst, size_t cap) {
     if (n == 0) return 0;
-    size_t need = 2 + 8 + (n + 1) * 10 + 16;
-    if (cap < need) return -5;
-    memset(dst, 0, need);
-    dst[0] = ENC_GORILLA;
-    dst[1] = 1 << 4;
-    uint64_t prev;
-    memcpy(&prev, &src[0], 8);
-    put_be64(dst + 2, prev);
-    size_t nb = 8 + 64; /* bit cursor relative to dst[1] */
-    auto put_bit = [&](int bit) {
-        if (bit) dst[(nb >> 3) + 1] |= uint8_t(128u >> (nb & 7));
-        nb++;
-    };
-    auto put_top = [&](uint64_t v, unsigned l) {
-        while (l > 0) {
-            unsigned m = nb & 7;
-            unsigned take = 8 - m;
-            if (take > l) take = l;
-            dst[(nb >> 3) + 1] |= uint8_t((v >> 56) >> m);
-            v <<= take;
-            nb += take;
-            l -= take;
-        }
-    };
-    uint64_t prev_lead = ~0ULL, prev_trail = 0;
-    for (size_t i = 1; i <= n; i++) {
-        uint64_t cur;
-        if (i < n) {
-            memcpy(&cur, &src[i], 8);
-            if (cur == SENTINEL) return -6;
-        } else {
-            cur = SENTINEL;
-        }
-        uint64_t x = cur ^ prev;
-        if (x == 0) { put_bit(0); prev = cur; continue; }
-        put_bit(1);
-        uint64_t lead = uint64_t(__builtin_clzll(x)) & 0x1f;
-        uint64_t trail = uint64_t(__builtin_ctzll(x));
-        if (prev_lead != ~0ULL && lead >= prev_lead && trail >= prev_trail) {
-            put_bit(0);
-            unsigned l = unsigned(64 - prev_lead - prev_trail);
-            uint64_t v = (l == 64) ? (x >> prev_trail) : ((x >> prev_trail) << (64 - l));
-            put_top(v, l);
-        } else {
-            prev_lead = lead;
-            prev_trail = trail;
-            put_bit(1);
-            put_top(lead << 59, 5);
-            uint64_t sig = 64 - lead - trail;
-            put_top(sig << 58, 6);
-            unsigned l = unsigned(sig);
-            uint64_t v = (l == 64) ? (x >> trail) : ((x >> trail) << (64 - l));
-            put_top(v, l);
-        }
-        prev = cur;
-    }
-    size_t length = (nb >> 3) + 1;
-    if (nb & 7) length += 1;
-    return int64_t(length);
+    if (cap < tsm_gorilla_max_len(n)) return GS_ERR_CAP;
+    return host_code(tsm_enc_gorilla(src, nullptr, n, dst));
 }
 
-/* bool_bitpack_encode, boolean.rs:24-64 */
 int64_t gs_encode_bool(const uint8_t *src, size_t n, uint8_t *dst, size_t cap) {
     if (n == 0) return 0;
-    size_t size = 1 + 8 + (n + 7) / 8;
-    if (cap < size + 2) return -5;
-    memset(dst, 0, size + 2);
-    dst[0] = ENC_BITPACK;
-    dst[1] = 1 << 4;
-    size_t vi = varint_put(dst + 2, uint64_t(n));
-    size_t nb = 8 + vi * 8;
-    for (size_t k = 0; k < n; k++) {
-        if (src[k]) dst[(nb >> 3) + 1] |= uint8_t(128u >> (nb & 7));
-        nb++;
-    }
-    size_t length = nb >> 3;
-    if (nb & 7) length += 1;
-    return int64_t(length + 1);
+    const size_t nb = (n + 7) / 8;
+    if (cap < 1 + 8 + nb + 2) return GS_ERR_CAP;
+    uint8_t *bits = dst + tsm_bool_header(dst, n);
+    for (size_t j = 0; j < nb; j++) bits[j] = tsm_bool_byte(src, n, j);
+    return int64_t(bits + nb - dst);
 }
 
-/* CRC-32/ISO-HDLC (crc32fast), page.rs:58-76 */
 uint32_t gs_crc32(const uint8_t *data, size_t len) {
-    static uint32_t table[256];
-    static bool init = false;
-    if (!init) {
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t c = i;
-            for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-            table[i] = c;
-        }
-        init = true;
-    }
-    uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < len; i++) c = table[(c ^ data[i]) & 0xFF] ^ (c >> 8);
-    return c ^ 0xFFFFFFFFu;
+    static const struct Table {
+        uint32_t t[256];
+        Table() { for (uint32_t i = 0; i < 256; i++) t[i] = tsm_crc32_entry(i); }
+    } table;
+    return tsm_crc32(table.t, data, len);
 }
 
 /* ---------------- string block encoder (codec/string.rs:32-88) ----------
@@ -392,17 +171,12 @@ int64_t gs_encode_str(const uint8_t *src, const uint64_t *lens, int64_t nstr,
                       uint8_t *dst, size_t cap) {
     if (nstr == 0) return 0;
     size_t payload = 0;
-    for (int64_t i = 0; i < nstr; i++) {
-        uint64_t v = lens[i];
-        payload += size_t(lens[i]);
-        do payload++; while ((v >>= 7));
-    }
+    for (int64_t i = 0; i < nstr; i++)
+        payload += size_t(lens[i]) + tsm_varint_len(lens[i]);
     std::vector<uint8_t> buf(payload);
     size_t p = 0, s = 0;
     for (int64_t i = 0; i < nstr; i++) {
-        uint64_t v = lens[i];
-        for (; v >= 0x80; v >>= 7) buf[p++] = uint8_t(v | 0x80);
-        buf[p++] = uint8_t(v);
+        p += tsm_varint_put(buf.data() + p, lens[i]);
         memcpy(buf.data() + p, src + s, size_t(lens[i]));
         p += size_t(lens[i]);
         s += size_t(lens[i]);
@@ -411,9 +185,7 @@ int64_t gs_encode_str(const uint8_t *src, const uint64_t *lens, int64_t nstr,
     dst[0] = 7;    /* Encoding::Snappy */
     dst[1] = 0x10; /* STRING_COMPRESSED_SNAPPY << 4 */
     uint8_t *op = dst + 2;
-    size_t v = payload;
-    for (; v >= 0x80; v >>= 7) *op++ = uint8_t(v | 0x80);
-    *op++ = uint8_t(v);
+    op += tsm_varint_put(op, payload);
     std::vector<uint16_t> tab(16384);
     for (size_t off = 0; off < payload; off += 65536) {
         size_t frag = payload - off < 65536 ? payload - off : 65536;
@@ -428,12 +200,8 @@ int64_t gs_build_page(const uint8_t *bitset, int64_t nrows, const uint8_t *data,
     size_t bl = size_t((nrows + 7) / 8);
     size_t total = 16 + bl + data_len;
     if (cap < total) return -5;
-    dst[0] = uint8_t(bl >> 24); dst[1] = uint8_t(bl >> 16);
-    dst[2] = uint8_t(bl >> 8); dst[3] = uint8_t(bl);
-    put_be64(dst + 4, uint64_t(nrows));
-    uint32_t crc = gs_crc32(data, data_len);
-    dst[12] = uint8_t(crc >> 24); dst[13] = uint8_t(crc >> 16);
-    dst[14] = uint8_t(crc >> 8); dst[15] = uint8_t(crc);
+    tsm_page_header(dst, uint32_t(bl), uint64_t(nrows),
+                    gs_crc32(data, data_len));
     memcpy(dst + 16, bitset, bl);
     memcpy(dst + 16 + bl, data, data_len);
     return int64_t(total);

@@ -20,6 +20,7 @@
 #include "../../include/cnosdb_gs.h"
 #include "gs_internal.h"
 #include "gs_gorilla.h"
+#include "gs_tsm_enc.h"
 
 /* hipError_t returns are checked with HIP_TRY on every path that can fail
  * user-visibly; cleanup paths (hipFree/hipEventDestroy in destructors) and
@@ -102,7 +103,7 @@ __device__ __forceinline__ bool dev_varint(const uint8_t *p, uint32_t len,
                            binary-search span/tombstone kernels; fail
                            loudly instead (the reference's row-wise
                            filtering cannot mis-select) */
-/* raised by k_encode_pages only, read by gs_encode_pages_dev */
+/* raised by the encode kernels only, read by enc_dev_status */
 #define DERR_ENC_SENTINEL 8u /* Gorilla sentinel as an input value */
 #define DERR_ENC_NULL 16u    /* null row in a ts/i64 page */
 
@@ -2966,10 +2967,11 @@ __global__ void k_agg_fixup(const DevAggMeta *__restrict__ pc_meta,
 /* --------------------------------------------------- GPU page re-encode
  * The write side of compaction (tsm/writer.rs:249-314 via
  * Page::arrow_array_to_page, tsm/page.rs:100-353): one thread per output
- * page, byte-exact with the host encoders in gs_encode.cpp (which are
- * pinned by the reference's golden vectors).  ts/i64 multi-pass encoders
- * require all-valid input (time columns are never null; i64 nulls are a
- * later row); Gorilla streams past nulls inline. */
+ * page running the encoders of gs_tsm_enc.h, the functions the host entry
+ * points of gs_encode.cpp run (pinned by the reference's golden vectors).
+ * The ts/i64 encoder is multi-pass and wants all-valid input (time columns
+ * are never null; k_enc_prepare densifies i64 columns first); Gorilla
+ * streams past nulls inline. */
 
 struct EncPageSpec {
     int64_t row_off;
@@ -2977,224 +2979,29 @@ struct EncPageSpec {
     int32_t pad;
 };
 
-/* MSB-first bit appender emitting bytes to global memory */
-struct DevBitWriter {
-    uint8_t *dst;
-    int64_t nbytes;
-    uint64_t acc; /* filled from the top */
-    int nfill;
-    __device__ void init(uint8_t *d) { dst = d; nbytes = 0; acc = 0; nfill = 0; }
-    __device__ __forceinline__ void put(uint64_t x, int l) { /* l <= 32 */
-        acc |= (x & ((l == 64) ? ~0ULL : ((1ULL << l) - 1))) << (64 - nfill - l);
-        nfill += l;
-        while (nfill >= 8) {
-            dst[nbytes++] = uint8_t(acc >> 56);
-            acc <<= 8;
-            nfill -= 8;
-        }
-    }
-    __device__ __forceinline__ void put64(uint64_t x, int l) {
-        if (l > 32) { put(x >> 32, l - 32); put(x & 0xffffffffULL, 32); }
-        else if (l > 0) put(x, l);
-    }
-    __device__ int64_t finish() { /* pad final partial byte with zeros */
-        if (nfill > 0) { dst[nbytes++] = uint8_t(acc >> 56); acc = 0; nfill = 0; }
-        return nbytes;
-    }
-};
-
-__device__ __forceinline__ void dev_put_be64(uint8_t *p, uint64_t v) {
-    for (int i = 7; i >= 0; i--) { p[i] = uint8_t(v); v >>= 8; }
-}
-__device__ __forceinline__ uint64_t dev_zzenc(int64_t v) {
-    return (uint64_t(v) << 1) ^ uint64_t(v >> 63);
-}
-__device__ int dev_varint_put(uint8_t *dst, uint64_t v) {
-    int n = 0;
-    while (v >= 0x80) { dst[n++] = uint8_t(v | 0x80); v >>= 7; }
-    dst[n++] = uint8_t(v);
-    return n;
+/* the block's CRC table in LDS, built cooperatively */
+__device__ __forceinline__ void enc_crc_table(uint32_t *crct) {
+    for (int i = threadIdx.x; i < 256; i += blockDim.x)
+        crct[i] = tsm_crc32_entry(uint32_t(i));
+    __syncthreads();
 }
 
-__constant__ uint8_t DEV_S8B_NUM_BITS[14][2] = {
-    {60, 1}, {30, 2}, {20, 3}, {15, 4}, {12, 5}, {10, 6}, {8, 7},
-    {7, 8},  {6, 10}, {5, 12}, {4, 15}, {3, 20}, {2, 30}, {1, 60},
-};
-
-/* Gorilla f64 encode of one page's non-null values (float.rs:32-243);
- * returns data length or -1 (sentinel input) */
-__device__ int64_t dev_enc_gorilla(const double *v, const uint8_t *valid,
-                                   int64_t row_off, int32_t nrows,
-                                   uint8_t *dst) {
-    /* find first non-null */
-    int32_t r0 = 0;
-    if (valid) while (r0 < nrows && !valid[row_off + r0]) r0++;
-    if (r0 >= nrows) return 0; /* empty input -> empty buffer */
-    dst[0] = GS_ENC_GORILLA;
-    dst[1] = 1 << 4;
-    uint64_t prev = (uint64_t)__double_as_longlong(v[row_off + r0]);
-    dev_put_be64(dst + 2, prev);
-    DevBitWriter bw;
-    bw.init(dst + 10);
-    uint64_t prev_lead = ~0ULL, prev_trail = 0;
-    int32_t r = r0 + 1;
-    for (;;) {
-        uint64_t cur;
-        if (r < nrows) {
-            if (valid && !valid[row_off + r]) { r++; continue; }
-            cur = (uint64_t)__double_as_longlong(v[row_off + r]);
-            r++;
-            if (cur == GORILLA_SENTINEL) return -1;
-        } else {
-            cur = GORILLA_SENTINEL;
-        }
-        uint64_t x = cur ^ prev;
-        if (x == 0) {
-            bw.put(0, 1);
-            prev = cur;
-            if (cur == GORILLA_SENTINEL) break;
-            continue;
-        }
-        bw.put(1, 1);
-        uint64_t lead = uint64_t(__builtin_clzll(x)) & 0x1f;
-        uint64_t trail = uint64_t(__builtin_ctzll(x));
-        if (prev_lead != ~0ULL && lead >= prev_lead && trail >= prev_trail) {
-            bw.put(0, 1);
-            int l = int(64 - prev_lead - prev_trail);
-            bw.put64(x >> prev_trail, l);
-        } else {
-            prev_lead = lead;
-            prev_trail = trail;
-            bw.put(1, 1);
-            bw.put(lead, 5);
-            uint64_t sig = 64 - lead - trail;
-            bw.put(sig & 0x3f, 6); /* 64 encodes as 0 */
-            bw.put64(x >> trail, int(sig));
-        }
-        prev = cur;
-        if (cur == GORILLA_SENTINEL) break;
+/* Ends one page's encode.  dl is what the encoder returned: an error is
+ * raised and handed on as the page's length, else the page gets its crc
+ * and header (bl = bitset bytes) and its full length comes back. */
+__device__ __forceinline__ int64_t enc_seal_page(
+    uint8_t *pg, uint32_t bl, int32_t nrows, const uint8_t *data, int64_t dl,
+    const uint32_t *crct, unsigned *err) {
+    if (dl < 0) {
+        atomicOr(err, dl == TSM_ENC_ERR_SENTINEL ? DERR_ENC_SENTINEL
+                                                 : DERR_FORMAT);
+        return dl;
     }
-    return 10 + bw.finish();
+    tsm_page_header(pg, bl, uint64_t(nrows), tsm_crc32(crct, data, size_t(dl)));
+    return 16 + int64_t(bl) + dl;
 }
 
-/* delta/zigzag int encode of one all-valid page (timestamp.rs:51-122 /
- * integer.rs:40-96), multi-pass over the input; returns data length */
-__device__ int64_t dev_enc_int(const int64_t *v, int64_t row_off,
-                               int32_t n, uint8_t *dst, bool is_ts) {
-    if (n == 0) return 0;
-    const int64_t *s = v + row_off;
-    auto rawd = [&](int32_t i) { /* wrapping diff, u64 */
-        return uint64_t(s[i]) - uint64_t(s[i - 1]);
-    };
-    size_t w = 0;
-    dst[w++] = is_ts ? GS_ENC_DELTATS : GS_ENC_DELTA;
-    /* pass 1: max + RLE check */
-    uint64_t max = 0, d1 = 0;
-    bool use_rle = true;
-    for (int32_t i = 1; i < n; i++) {
-        uint64_t d = rawd(i);
-        if (!is_ts) d = dev_zzenc(int64_t(d));
-        if (i == 1) d1 = d;
-        else if (d != d1) use_rle = false;
-        if (d > max) max = d;
-    }
-    uint64_t d0 = is_ts ? uint64_t(s[0]) : dev_zzenc(s[0]);
-    if ((is_ts && n > 1 && use_rle) || (!is_ts && n > 2 && use_rle)) {
-        dst[w++] = 0;
-        dev_put_be64(dst + w, d0);
-        w += 8;
-        if (is_ts) {
-            uint64_t div = 1000000000000ULL;
-            while (div > 1 && d1 % div != 0) div /= 10;
-            if (div > 1) {
-                unsigned sc = 0;
-                for (uint64_t x = div; x > 1; x /= 10) sc++;
-                dst[1] |= uint8_t(sc);
-                w += dev_varint_put(dst + w, d1 / div);
-            } else {
-                w += dev_varint_put(dst + w, d1);
-            }
-            w += dev_varint_put(dst + w, uint64_t(n));
-        } else {
-            w += dev_varint_put(dst + w, d1);
-            w += dev_varint_put(dst + w, uint64_t(n) - 1);
-        }
-        dst[1] |= uint8_t(2 << 4);
-        return int64_t(w);
-    }
-    if (max > ((1ULL << 60) - 1)) { /* uncompressed */
-        dst[w++] = 0;
-        dev_put_be64(dst + w, d0);
-        w += 8;
-        for (int32_t i = 1; i < n; i++) {
-            uint64_t d = rawd(i);
-            if (!is_ts) d = dev_zzenc(int64_t(d));
-            dev_put_be64(dst + w, d);
-            w += 8;
-        }
-        return int64_t(w);
-    }
-    /* simple8b; ts applies the power-of-10 divisor (timestamp.rs:97-121) */
-    uint64_t div = 1;
-    unsigned sc = 0;
-    if (is_ts) {
-        div = 1000000000000ULL;
-        for (int32_t i = 1; i < n && div > 1; i++)
-            while (div > 1 && rawd(i) % div != 0) div /= 10;
-        for (uint64_t x = div; x > 1; x /= 10) sc++;
-    }
-    auto packed = [&](int32_t j) { /* j in 0..n-2 */
-        uint64_t d = rawd(j + 1);
-        return is_ts ? d / div : dev_zzenc(int64_t(d));
-    };
-    dst[w++] = uint8_t((1 << 4) | sc);
-    dev_put_be64(dst + w, d0);
-    w += 8;
-    /* simple8b greedy packer (simple8b.rs:26-76) */
-    int32_t m = n - 1, i = 0;
-    while (i < m) {
-        int32_t remain = m - i;
-        if (remain >= 120) {
-            int32_t lim = remain >= 240 ? 240 : 120;
-            int32_t k = 0;
-            while (k < lim && packed(i + k) == 1) k++;
-            if (k == 240) {
-                for (int q = 0; q < 8; q++) dst[w + q] = 0;
-                w += 8; i += 240;
-                continue;
-            }
-            if (k >= 120) {
-                dev_put_be64(dst + w, 1ULL << 60);
-                w += 8; i += 120;
-                continue;
-            }
-        }
-        bool ok = false;
-        for (int idx = 0; idx < 14; idx++) {
-            int32_t int_n = DEV_S8B_NUM_BITS[idx][0];
-            unsigned bit_n = DEV_S8B_NUM_BITS[idx][1];
-            if (int_n > remain) continue;
-            uint64_t max_val = 1ULL << (bit_n & 0x3f);
-            uint64_t word = (uint64_t(idx) + 2) << 60;
-            bool fits = true;
-            for (int32_t q = 0; q < int_n; q++) {
-                uint64_t pv = packed(i + q);
-                if (pv >= max_val) { fits = false; break; }
-                word |= pv << ((unsigned(q) * bit_n) & 0x3f);
-            }
-            if (!fits) continue;
-            dev_put_be64(dst + w, word);
-            w += 8; i += int_n;
-            ok = true;
-            break;
-        }
-        if (!ok) return -2; /* value out of bounds */
-    }
-    return int64_t(w);
-}
-
-/* one thread per output page: bitset + encode + crc + header
- * (page layout tsm/page.rs:488-497) */
+/* one thread per output page: bitset + encode + seal */
 __global__ void k_encode_pages(int kind /*0=ts 1=i64 2=f64*/,
                                const void *__restrict__ vals,
                                const uint8_t *__restrict__ valid,
@@ -3202,14 +3009,8 @@ __global__ void k_encode_pages(int kind /*0=ts 1=i64 2=f64*/,
                                int npages, uint8_t *__restrict__ out,
                                int64_t cap, int64_t *__restrict__ lens,
                                unsigned *__restrict__ err) {
-    /* crc32 table built cooperatively in LDS (CRC-32/ISO-HDLC) */
     __shared__ uint32_t crct[256];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        crct[i] = c;
-    }
-    __syncthreads();
+    enc_crc_table(crct);
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npages;
          p += gridDim.x * blockDim.x) {
         EncPageSpec ps = pages[p];
@@ -3227,10 +3028,11 @@ __global__ void k_encode_pages(int kind /*0=ts 1=i64 2=f64*/,
             bs[b] = byte;
         }
         uint8_t *data = pg + 16 + bl;
+        const size_t n = ps.nrows > 0 ? size_t(ps.nrows) : 0;
         int64_t dl;
         if (kind == 2) {
-            dl = dev_enc_gorilla((const double *)vals, valid, ps.row_off,
-                                 ps.nrows, data);
+            dl = tsm_enc_gorilla((const double *)vals + ps.row_off,
+                                 valid ? valid + ps.row_off : nullptr, n, data);
         } else {
             if (valid) { /* int encoders need all-valid input (see header) */
                 bool av = true;
@@ -3238,25 +3040,10 @@ __global__ void k_encode_pages(int kind /*0=ts 1=i64 2=f64*/,
                     if (!valid[ps.row_off + r]) { av = false; break; }
                 if (!av) { atomicOr(err, DERR_ENC_NULL); lens[p] = -3; continue; }
             }
-            dl = dev_enc_int((const int64_t *)vals, ps.row_off, ps.nrows,
-                             data, kind == 0);
+            dl = tsm_enc_int(kind == 0, (const int64_t *)vals + ps.row_off, n,
+                             data, nullptr);
         }
-        if (dl < 0) {
-            /* -1: dev_enc_gorilla met the sentinel; -2: dev_enc_int */
-            atomicOr(err, dl == -1 ? DERR_ENC_SENTINEL : DERR_FORMAT);
-            lens[p] = dl;
-            continue;
-        }
-        uint32_t crc = 0xFFFFFFFFu;
-        for (int64_t i = 0; i < dl; i++)
-            crc = crct[(crc ^ data[i]) & 0xFF] ^ (crc >> 8);
-        crc ^= 0xFFFFFFFFu;
-        pg[0] = uint8_t(bl >> 24); pg[1] = uint8_t(bl >> 16);
-        pg[2] = uint8_t(bl >> 8); pg[3] = uint8_t(bl);
-        dev_put_be64(pg + 4, uint64_t(ps.nrows));
-        pg[12] = uint8_t(crc >> 24); pg[13] = uint8_t(crc >> 16);
-        pg[14] = uint8_t(crc >> 8); pg[15] = uint8_t(crc);
-        lens[p] = 16 + int64_t(bl) + dl;
+        lens[p] = enc_seal_page(pg, bl, ps.nrows, data, dl, crct, err);
     }
 }
 
@@ -3264,7 +3051,7 @@ __global__ void k_encode_pages(int kind /*0=ts 1=i64 2=f64*/,
  * every column of a merged column group in two launches.  k_enc_prepare
  * does the per-page work that parallelises (bitset, null densification,
  * count, statistics, bool packing), one block per (column, page);
- * k_enc_group_pages then runs the serial int/Gorilla encoders above over
+ * k_enc_group_pages then runs the serial int/Gorilla encoders over
  * the dense values, one thread per (column, page), and seals the page. */
 
 struct EncGroupCol {
@@ -3309,10 +3096,6 @@ __device__ __forceinline__ void enc_min_merge(int ct, uint64_t &a, int32_t &ra,
 __device__ __forceinline__ void enc_max_merge(int ct, uint64_t &a, int32_t &ra,
                                               uint64_t b, int32_t rb) {
     if (enc_lt(ct, a, b) || (enc_eq(ct, b, a) && rb < ra)) { a = b; ra = rb; }
-}
-__device__ __forceinline__ int dev_varint_len(uint32_t v) {
-    return 1 + (v >= (1u << 7)) + (v >= (1u << 14)) + (v >= (1u << 21)) +
-           (v >= (1u << 28));
 }
 
 /* One block per (column, page), work item w = c*npages + p.  Each step
@@ -3425,33 +3208,23 @@ __global__ __launch_bounds__(ENC_PREP_THREADS) void k_enc_prepare(
             info[w].max_bits = mx;
         }
         if (is_bool && nn > 0) {
-            /* bool_bitpack_encode (boolean.rs:24-64): [10][1<<4][varint n]
-               then the values MSB-first from a byte boundary; one output
-               byte per thread from 8 dense bytes */
+            /* the bool block (gs_tsm_enc.h): thread 0 writes the header,
+               every thread its share of the bit area, one output byte from
+               8 dense bytes at a time */
             const uint8_t *src = vd ? (const uint8_t *)col.dense + ps.row_off : v1;
             uint8_t *data = bs + bl;
-            const int vi = dev_varint_len(uint32_t(nn));
-            if (threadIdx.x == 0) {
-                data[0] = GS_ENC_BITPACK;
-                data[1] = 1 << 4;
-                dev_varint_put(data + 2, uint64_t(nn));
-            }
+            if (threadIdx.x == 0) tsm_bool_header(data, uint64_t(nn));
+            uint8_t *bits = data + tsm_bool_header_len(uint64_t(nn));
             const int32_t nb = (nn + 7) / 8;
-            for (int32_t j = threadIdx.x; j < nb; j += ENC_PREP_THREADS) {
-                uint8_t byte = 0;
-                for (int k = 0; k < 8; k++) {
-                    int32_t i = j * 8 + k;
-                    if (i < nn && src[i]) byte |= uint8_t(0x80u >> k);
-                }
-                data[2 + vi + j] = byte;
-            }
+            for (int32_t j = threadIdx.x; j < nb; j += ENC_PREP_THREADS)
+                bits[j] = tsm_bool_byte(src, size_t(nn), size_t(j));
         }
         __syncthreads(); /* smin.. are rewritten by the next work item */
     }
 }
 
-/* one thread per (column, page): encode the dense values, then crc and
- * header as in k_encode_pages */
+/* one thread per (column, page): encode the dense values and seal the
+ * page, as k_encode_pages does */
 __global__ void k_enc_group_pages(const EncGroupCol *__restrict__ cols,
                                   int ncols,
                                   const EncPageSpec *__restrict__ pages,
@@ -3459,12 +3232,7 @@ __global__ void k_enc_group_pages(const EncGroupCol *__restrict__ cols,
                                   GsPageInfo *__restrict__ info,
                                   unsigned *__restrict__ err) {
     __shared__ uint32_t crct[256];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        crct[i] = c;
-    }
-    __syncthreads();
+    enc_crc_table(crct);
     const int nwork = ncols * npages;
     for (int w = blockIdx.x * blockDim.x + threadIdx.x; w < nwork;
          w += gridDim.x * blockDim.x) {
@@ -3483,28 +3251,15 @@ __global__ void k_enc_group_pages(const EncGroupCol *__restrict__ cols,
         const void *src = col.dense ? col.dense : col.vals;
         int64_t dl;
         if (col.ctype == GS_CT_F64)
-            dl = dev_enc_gorilla((const double *)src, nullptr, ps.row_off, nn,
-                                 data);
+            dl = tsm_enc_gorilla((const double *)src + ps.row_off, nullptr,
+                                 size_t(nn), data);
         else if (col.ctype == GS_CT_BOOL) /* packed by k_enc_prepare */
-            dl = nn ? 2 + dev_varint_len(uint32_t(nn)) + (nn + 7) / 8 : 0;
+            dl = int64_t(tsm_bool_len(uint64_t(nn)));
         else /* u64 is the i64 codec over the same bits (unsigned.rs:15-18) */
-            dl = dev_enc_int((const int64_t *)src, ps.row_off, nn, data,
-                             col.ctype == GS_CT_TIME);
-        if (dl < 0) {
-            atomicOr(err, dl == -1 ? DERR_ENC_SENTINEL : DERR_FORMAT);
-            info[w].len = dl;
-            continue;
-        }
-        uint32_t crc = 0xFFFFFFFFu;
-        for (int64_t i = 0; i < dl; i++)
-            crc = crct[(crc ^ data[i]) & 0xFF] ^ (crc >> 8);
-        crc ^= 0xFFFFFFFFu;
-        pg[0] = uint8_t(bl >> 24); pg[1] = uint8_t(bl >> 16);
-        pg[2] = uint8_t(bl >> 8); pg[3] = uint8_t(bl);
-        dev_put_be64(pg + 4, uint64_t(ps.nrows));
-        pg[12] = uint8_t(crc >> 24); pg[13] = uint8_t(crc >> 16);
-        pg[14] = uint8_t(crc >> 8); pg[15] = uint8_t(crc);
-        info[w].len = 16 + int64_t(bl) + dl;
+            dl = tsm_enc_int(col.ctype == GS_CT_TIME,
+                             (const int64_t *)src + ps.row_off, size_t(nn),
+                             data, nullptr);
+        info[w].len = enc_seal_page(pg, bl, ps.nrows, data, dl, crct, err);
     }
 }
 
@@ -5231,6 +4986,29 @@ GsStatus gs_scan(GsCtx *ctx, GsGroupSet *set, const GsScanSpec *spec,
     return GS_OK;
 }
 
+/* Worst-case data block of an 8-byte column page of maxr rows, as the
+ * device entry points ask for it (ints: 16 bytes above the host's
+ * threshold, see tsm_int_max_len). */
+static int64_t enc_dev_max_len(bool f64, int64_t maxr) {
+    return f64 ? int64_t(tsm_gorilla_max_len(uint64_t(maxr)))
+               : int64_t(tsm_int_max_len(uint64_t(maxr))) + 16;
+}
+
+/* After an encode launch: the encoders' own error surface.  Pages (cells)
+ * that failed have a negative length, every other one of the launch is
+ * complete. */
+static GsStatus enc_dev_status(GsCtx *ctx, const char *null_row_msg) {
+    unsigned e = 0;
+    HIP_TRY(hipMemcpy(&e, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (!e) return GS_OK;
+    hipMemset(ctx->d_err, 0, sizeof(unsigned));
+    if (e & DERR_ENC_SENTINEL)
+        return fail(GS_ERR_SENTINEL,
+                    "encode: Gorilla sentinel value in the input");
+    if (e & DERR_ENC_NULL) return fail(GS_ERR_FORMAT, null_row_msg);
+    return fail(GS_ERR_FORMAT, "encode: value out of simple8b range");
+}
+
 GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
                              const uint8_t *d_valid, const int64_t *h_row_off,
                              const int32_t *h_rows, int32_t npages,
@@ -5242,9 +5020,7 @@ GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
     int32_t maxr = 0;
     for (int32_t p = 0; p < npages; p++) if (h_rows[p] > maxr) maxr = h_rows[p];
     /* worst case: ints -> uncompressed 8 B/val; f64 -> ~77 bits/val */
-    int64_t need = 16 + (int64_t(maxr) + 7) / 8 +
-                   (kind == 2 ? (2 + 8 + (int64_t(maxr) + 1) * 10 + 16)
-                              : (2 + 8 * int64_t(maxr) + 32));
+    int64_t need = 16 + (int64_t(maxr) + 7) / 8 + enc_dev_max_len(kind == 2, maxr);
     if (cap_per_page < need)
         return fail(GS_ERR_CAP, "cap_per_page below worst-case encoded size");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -5273,20 +5049,8 @@ GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
     hipFree(d_specs);
     hipFree(d_lens);
     if (st != GS_OK) return st;
-    /* the encoder's own error surface: pages that failed have a negative
-       h_lens entry, every other page of the launch is complete */
-    unsigned e = 0;
-    HIP_TRY(hipMemcpy(&e, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (!e) return GS_OK;
-    hipMemset(ctx->d_err, 0, sizeof(unsigned));
-    if (e & DERR_ENC_SENTINEL)
-        return fail(GS_ERR_SENTINEL,
-                    "encode: Gorilla sentinel value in the input");
-    if (e & DERR_ENC_NULL)
-        return fail(GS_ERR_FORMAT,
-                    "encode: null row in a ts/i64 page (integer pages must "
-                    "be all-valid)");
-    return fail(GS_ERR_FORMAT, "encode: value out of simple8b range");
+    return enc_dev_status(ctx, "encode: null row in a ts/i64 page (integer "
+                               "pages must be all-valid)");
 }
 
 GsStatus gs_encode_group_pages_dev(GsCtx *ctx, int32_t ncols,
@@ -5331,9 +5095,8 @@ GsStatus gs_encode_group_pages_dev(GsCtx *ctx, int32_t ncols,
         /* worst case: ints -> uncompressed 8 B/val; f64 -> ~77 bits/val;
            bool -> header, 10-byte varint bound and one bit per value */
         int64_t need = 16 + (maxr + 7) / 8;
-        if (ctype[c] == GS_CT_F64) need += 2 + 8 + (maxr + 1) * 10 + 16;
-        else if (ctype[c] == GS_CT_BOOL) need += 2 + 10 + (maxr + 7) / 8;
-        else need += 2 + 8 * maxr + 32;
+        if (ctype[c] == GS_CT_BOOL) need += 2 + 10 + (maxr + 7) / 8;
+        else need += enc_dev_max_len(ctype[c] == GS_CT_F64, maxr);
         if (cap_per_page[c] < need)
             return fail(GS_ERR_CAP, "gs_encode_group_pages_dev: cap_per_page "
                                     "below worst-case encoded size");
@@ -5400,18 +5163,7 @@ GsStatus gs_encode_group_pages_dev(GsCtx *ctx, int32_t ncols,
         st = fail(GS_ERR, "group encode: page info readback failed");
     release();
     if (st != GS_OK) return st;
-    /* same error surface as gs_encode_pages_dev: failed cells have a
-       negative len, every other cell of the launch is complete */
-    unsigned e = 0;
-    HIP_TRY(hipMemcpy(&e, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (!e) return GS_OK;
-    hipMemset(ctx->d_err, 0, sizeof(unsigned));
-    if (e & DERR_ENC_SENTINEL)
-        return fail(GS_ERR_SENTINEL,
-                    "encode: Gorilla sentinel value in the input");
-    if (e & DERR_ENC_NULL)
-        return fail(GS_ERR_FORMAT, "encode: null row in the time column");
-    return fail(GS_ERR_FORMAT, "encode: value out of simple8b range");
+    return enc_dev_status(ctx, "encode: null row in the time column");
 }
 
 /* Host-side setup shared by both merge entries: everything that depends

@@ -41,8 +41,6 @@
 #define GOR_FN inline
 #endif
 
-#define GORILLA_SENTINEL 0x7ff8000000000ffULL
-
 /* Parser window state.  hi:lo is a 128-bit window holding nb valid bits,
  * left-aligned; nextw/nextw2 are the two words prefetched behind it. */
 struct GorChunkState {

@@ -5,6 +5,10 @@
 #include <cstdint>
 #include <cstddef>
 
+/* The f64 value that ends a Gorilla bitstream (float.rs:16); read by the
+ * parser of gs_gorilla.h and written by the encoder of gs_tsm_enc.h. */
+#define GORILLA_SENTINEL 0x7ff8000000000ffULL
+
 /* Device-side page descriptor. Offsets index the set's blob buffer.
  * data region of each page is 16-byte aligned within the blob. */
 struct DevPage {

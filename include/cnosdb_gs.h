@@ -302,8 +302,10 @@ GsStatus gs_scan_wait(GsCtx *ctx, GsGroupSet *set, GsScanResult *result);
  * Page::arrow_array_to_page, tsm/page.rs:100-353 + tsm/writer.rs:249-314).
  * kind: 0 = ts (DeltaTs), 1 = i64 (Delta), 2 = f64 (Gorilla).  d_vals is a
  * device column; pages are [h_row_off[p], +h_rows[p]) slices.  Each full
- * page (header+crc+bitset+data, byte-exact with the host encoder) is
- * written at d_out + p*cap_per_page; h_lens receives encoded lengths.
+ * page (header+crc+bitset+data; the data block comes from the functions
+ * gs_encode_* run on the host, csrc/gs_tsm_enc.h, so it is theirs byte for
+ * byte) is written at d_out + p*cap_per_page; h_lens receives encoded
+ * lengths.
  * Int encoders (kind 0/1) require all-valid slices — the time column is
  * never null.  Null-carrying i64, u64 and bool columns, and the page
  * statistics, are gs_encode_group_pages_dev's (below), which encodes a
@@ -325,8 +327,9 @@ GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
  * gs_compact_merge_fields) ----
  * Takes the merged columns as that call leaves them — the time column plus
  * up to GS_MAX_MERGE_COLS i64/u64/f64/bool field columns, validity bytes
- * and all — and writes every page of every column, each byte-exact with
- * the host path (gs_encode_* over the non-null values + gs_build_page).
+ * and all — and writes every page of every column, each the page of the
+ * host path (gs_encode_* over the non-null values + gs_build_page), whose
+ * encoders, CRC and page header are the same functions (csrc/gs_tsm_enc.h).
  * The page split h_row_off/h_rows is shared by all columns.  u64 is the
  * i64 codec over the same bits (codec/unsigned.rs:15-18); an all-null or
  * zero-row page has an empty data region.  Value slots of null rows are
