@@ -29,6 +29,7 @@
  * deferred error.  Silence the nodiscard noise for those. */
 #pragma clang diagnostic ignored "-Wunused-value"
 
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -3271,11 +3272,35 @@ struct GsCtx {
     unsigned *d_err;
 };
 
-static int grid_for(int work, int per_block) {
-    int blocks = (work + per_block - 1) / per_block;
-    if (blocks > 2048) blocks = 2048; /* grid-stride beyond (Guideline 11) */
-    if (blocks < 1) blocks = 1;
-    return blocks;
+/* Every capped launch takes its grid from grid_for or grid_items, so one
+   debug override (gs_debug_set_grid_cap) can drive any kernel through
+   several trips of its grid-stride loop on a set of a few thousand pages.
+   g_grid_cap <= 0: no override.  g_grid_rounds: the largest
+   ceil(uncapped blocks / granted blocks) seen since the last reset. */
+static std::atomic<int> g_grid_cap{0};
+static std::atomic<int> g_grid_rounds{0};
+
+/* one item per block: min(items, the site's cap), block-stride beyond */
+static int grid_items(int64_t want, int cap) {
+    int64_t g = want > cap ? cap : want;
+    int dbg = g_grid_cap.load(std::memory_order_relaxed);
+    if (dbg > 0 && g > dbg) g = dbg;
+    if (g > 0) {
+        int64_t trips = (want + g - 1) / g;
+        int r = trips > INT32_MAX ? INT32_MAX : int(trips);
+        int seen = g_grid_rounds.load(std::memory_order_relaxed);
+        while (r > seen && !g_grid_rounds.compare_exchange_weak(
+                               seen, r, std::memory_order_relaxed)) {
+        }
+    }
+    return int(g);
+}
+
+/* one item per thread (or per per_block-thread block): at most 2048 blocks,
+   grid-stride beyond (Guideline 11) */
+static int grid_for(int64_t work, int per_block) {
+    int64_t want = (work + per_block - 1) / per_block;
+    return grid_items(want < 1 ? 1 : want, 2048);
 }
 
 struct SlotPages {
@@ -3984,6 +4009,21 @@ int64_t gs_debug_kernel_crc(GsCtx *ctx, GsGroupSet *set, uint64_t off,
     return 0;
 }
 
+/* debug (test seam): cap every capped launch at max_blocks, so that small
+   sets drive the kernels through several trips of their stride loops.
+   <= 0 restores the defaults.  Returns the previous setting. */
+int32_t gs_debug_set_grid_cap(int32_t max_blocks) {
+    return g_grid_cap.exchange(max_blocks > 0 ? max_blocks : 0,
+                               std::memory_order_relaxed);
+}
+
+/* debug: the largest ceil(uncapped blocks / granted blocks) of any capped
+   launch since the last reset */
+int32_t gs_debug_grid_rounds(int reset) {
+    return reset ? g_grid_rounds.exchange(0, std::memory_order_relaxed)
+                 : g_grid_rounds.load(std::memory_order_relaxed);
+}
+
 int64_t gs_set_rows(const GsGroupSet *set) { return set ? set->total_rows : -1; }
 int64_t gs_set_series(const GsGroupSet *set) { return set ? set->nsgroups : -1; }
 
@@ -4157,7 +4197,7 @@ GsStatus gs_decode(GsCtx *ctx, GsGroupSet *set, uint32_t col, void *d_out,
                            sp.d_gor_chunks, n, (double *)d_out, ctx->d_err);
         if (d_valid)
             hipLaunchKernelGGL(k_valid_fill,
-                               dim3(sp.n[PC_GOR] > 2048 ? 2048 : sp.n[PC_GOR]),
+                               dim3(grid_items(sp.n[PC_GOR], 2048)),
                                dim3(256), 0, ctx->stream, sp.dev[PC_GOR],
                                sp.n[PC_GOR], d_valid);
     }
@@ -4169,37 +4209,37 @@ GsStatus gs_decode(GsCtx *ctx, GsGroupSet *set, uint32_t col, void *d_out,
         if (d_valid)
             hipLaunchKernelGGL(
                 k_valid_expand,
-                dim3(sp.n[PC_GORN] > 2048 ? 2048 : sp.n[PC_GORN]), dim3(256),
+                dim3(grid_items(sp.n[PC_GORN], 2048)), dim3(256),
                 0, ctx->stream, set->d_blob, sp.dev[PC_GORN], sp.n[PC_GORN],
                 d_valid);
     }
     if (sp.n[PC_S8B]) {
         int n = sp.n[PC_S8B];
-        hipLaunchKernelGGL(k_s8b_par, dim3(n > 65535 ? 65535 : n), dim3(256),
+        hipLaunchKernelGGL(k_s8b_par, dim3(grid_items(n, 65535)), dim3(256),
                            0, ctx->stream, set->d_blob, sp.dev[PC_S8B], n,
                            (int64_t *)d_out, d_valid, ctx->d_err);
     }
     if (sp.n[PC_BOOL]) {
         int n = sp.n[PC_BOOL];
-        hipLaunchKernelGGL(k_bool_par, dim3(n > 65535 ? 65535 : n), dim3(256),
+        hipLaunchKernelGGL(k_bool_par, dim3(grid_items(n, 65535)), dim3(256),
                            0, ctx->stream, set->d_blob, sp.dev[PC_BOOL], n,
                            (uint8_t *)d_out, d_valid, ctx->d_err);
     }
     if (sp.n[PC_RAW]) {
         int n = sp.n[PC_RAW];
-        hipLaunchKernelGGL(k_raw_par, dim3(n > 65535 ? 65535 : n), dim3(256),
+        hipLaunchKernelGGL(k_raw_par, dim3(grid_items(n, 65535)), dim3(256),
                            0, ctx->stream, set->d_blob, sp.dev[PC_RAW], n,
                            (int64_t *)d_out, d_valid, ctx->d_err);
     }
     if (sp.n[PC_RLE_TS])
         hipLaunchKernelGGL(k_rle_par,
-                           dim3(sp.n[PC_RLE_TS] > 2048 ? 2048 : sp.n[PC_RLE_TS]),
+                           dim3(grid_items(sp.n[PC_RLE_TS], 2048)),
                            dim3(256), 0, ctx->stream, set->d_blob,
                            sp.dev[PC_RLE_TS], sp.n[PC_RLE_TS], (int64_t *)d_out,
                            d_valid, 1, ctx->d_err);
     if (sp.n[PC_RLE_I64])
         hipLaunchKernelGGL(k_rle_par,
-                           dim3(sp.n[PC_RLE_I64] > 2048 ? 2048 : sp.n[PC_RLE_I64]),
+                           dim3(grid_items(sp.n[PC_RLE_I64], 2048)),
                            dim3(256), 0, ctx->stream, set->d_blob,
                            sp.dev[PC_RLE_I64], sp.n[PC_RLE_I64], (int64_t *)d_out,
                            d_valid, 0, ctx->d_err);
@@ -4295,9 +4335,7 @@ GsStatus gs_groupby_tag(GsCtx *ctx, GsGroupSet *set, int tag_col,
                    hipMemcpyHostToDevice, ctx->stream);
     hipStreamSynchronize(ctx->stream);
     const int64_t total = int64_t(ngids) * n_buckets;
-    const int blocks = int(total > int64_t(2048) * 256
-                               ? 2048 : (total + 255) / 256);
-    hipLaunchKernelGGL(k_agg_tag, dim3(blocks < 1 ? 1 : blocks), dim3(256),
+    hipLaunchKernelGGL(k_agg_tag, dim3(grid_for(total, 256)), dim3(256),
                        0, ctx->stream, d_csr_off, d_csr_sg, ngids, n_buckets,
                        set->d_pmax, set->d_psum, set->d_pcnt, d_out_max,
                        d_out_sum, d_out_count);
@@ -4384,8 +4422,9 @@ GsStatus gs_apply_tombstone(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
     }
     HIP_TRY(hipMemcpyAsync(set->d_ranges, ranges, nranges * sizeof(GsTimeRange),
                            hipMemcpyHostToDevice, ctx->stream));
-    int blocks = int(set->ngroups > 2048 ? 2048 : set->ngroups);
-    hipLaunchKernelGGL(k_tombstone, dim3(blocks), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(k_tombstone,
+                       dim3(grid_items(int64_t(set->ngroups), 2048)),
+                       dim3(256), 0, ctx->stream,
                        set->d_groups, int(set->ngroups), d_ts, d_valid,
                        set->d_ranges, int(nranges));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -4465,10 +4504,9 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
     HIP_TRY(hipEventRecord(ev[SEV_OFFS], ctx->stream));
     /* at most every row of the set is selected: grid-stride beyond 2048
        blocks, and blocks past the device-side total exit at once */
-    int64_t tiles = (set->total_rows + GS_TS_TILE - 1) / GS_TS_TILE;
-    tiles = tiles < 1 ? 1 : (tiles > 2048 ? 2048 : tiles);
-    hipLaunchKernelGGL(k_rle_ts_tiles, dim3(int(tiles)), dim3(256), 0,
-                       ctx->stream, set->d_out_off, ng, set->d_g_t0sel,
+    hipLaunchKernelGGL(k_rle_ts_tiles,
+                       dim3(grid_for(set->total_rows, GS_TS_TILE)),
+                       dim3(256), 0, ctx->stream, set->d_out_off, ng, set->d_g_t0sel,
                        set->d_g_delta, GS_TS_TILE, spec->d_out_ts);
     HIP_TRY(hipEventRecord(ev[SEV_TS], ctx->stream));
     int nsg = set->nsgroups;
@@ -4588,7 +4626,7 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
         if (spec->n_buckets > 0) {
             if (agg_fused) {
                 hipLaunchKernelGGL(k_agg_fixup,
-                                   dim3(nsg > 65535 ? 65535 : nsg),
+                                   dim3(grid_items(nsg, 65535)),
                                    dim3(256), shm_fix, ctx->stream,
                                    set->d_agg_meta, set->d_agg_val,
                                    fsp.d_sg_chunk_first,
@@ -4603,7 +4641,7 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                 }();
                 build_sgroups();
                 hipLaunchKernelGGL(k_agg_partial_rle,
-                                   dim3(nsg > 65535 ? 65535 : nsg),
+                                   dim3(grid_items(nsg, 65535)),
                                    dim3(agg_block), shm_rle, ctx->stream,
                                    set->d_sgroups_out, nsg,
                                    set->d_sgroup_first, set->d_g_t0sel,
@@ -4617,14 +4655,14 @@ static GsStatus scan_fused_launch(GsCtx *ctx, GsGroupSet *set,
                                      : 0;
                 build_sgroups();
                 hipLaunchKernelGGL(
-                    k_agg_partial, dim3(nsg > 65535 ? 65535 : nsg),
+                    k_agg_partial, dim3(grid_items(nsg, 65535)),
                     dim3(256), agg_shm, ctx->stream, set->d_sgroups_out,
                     nsg, spec->d_out_ts, d_val_f, nullptr, INT64_MIN,
                     INT64_MAX, spec->t0, spec->bucket_ns, spec->n_buckets,
                     set->d_pmax, set->d_psum, set->d_pcnt);
             }
             int mb = (spec->n_buckets + 3) / 4;
-            hipLaunchKernelGGL(k_agg_merge, dim3(mb > 2048 ? 2048 : mb),
+            hipLaunchKernelGGL(k_agg_merge, dim3(grid_items(mb, 2048)),
                                dim3(256), 0, ctx->stream, nsg,
                                spec->n_buckets, set->d_pmax, set->d_psum,
                                set->d_pcnt,
@@ -4886,7 +4924,7 @@ GsStatus gs_scan(GsCtx *ctx, GsGroupSet *set, const GsScanSpec *spec,
             const uint8_t fct = set->slots[1 + spec->field_col].ctype;
             vt = fct == GS_CT_I64 ? 1 : fct == GS_CT_U64 ? 2 : 0;
         }
-        hipLaunchKernelGGL(k_vmask, dim3(ng > 65535 ? 65535 : ng), dim3(256),
+        hipLaunchKernelGGL(k_vmask, dim3(grid_items(ng, 65535)), dim3(256),
                            0, ctx->stream, set->d_groups, ng, spec->d_val,
                            d_valid, set->d_sp_start, set->d_sp_cnt,
                            spec->value_pred.op, spec->value_pred.a,
@@ -4914,13 +4952,13 @@ GsStatus gs_scan(GsCtx *ctx, GsGroupSet *set, const GsScanSpec *spec,
         if (want_rows) {
             if (d_mask)
                 hipLaunchKernelGGL(k_compact_masked,
-                                   dim3(ng > 2048 ? 2048 : ng), dim3(256), 0,
+                                   dim3(grid_items(ng, 2048)), dim3(256), 0,
                                    ctx->stream, set->d_groups, ng, spec->d_ts,
                                    spec->d_val, d_mask, set->d_sp_start,
                                    set->d_sp_cnt, set->d_out_off,
                                    spec->d_out_ts, spec->d_out_val);
             else
-                hipLaunchKernelGGL(k_compact, dim3(ng > 2048 ? 2048 : ng),
+                hipLaunchKernelGGL(k_compact, dim3(grid_items(ng, 2048)),
                                    dim3(256), 0, ctx->stream, set->d_groups,
                                    ng, spec->d_ts, spec->d_val,
                                    set->d_sp_start, set->d_sp_cnt,
@@ -4947,7 +4985,7 @@ GsStatus gs_scan(GsCtx *ctx, GsGroupSet *set, const GsScanSpec *spec,
         }
         size_t agg_shm = spec->n_buckets <= 8192
                              ? (size_t(spec->n_buckets) + 1) * 4 : 0;
-        hipLaunchKernelGGL(k_agg_partial, dim3(nsg > 65535 ? 65535 : nsg),
+        hipLaunchKernelGGL(k_agg_partial, dim3(grid_items(nsg, 65535)),
                            dim3(256), agg_shm, ctx->stream, set->d_sgroups, nsg,
                            spec->d_ts, spec->d_val,
                            d_mask ? d_mask : d_valid,
@@ -4956,7 +4994,7 @@ GsStatus gs_scan(GsCtx *ctx, GsGroupSet *set, const GsScanSpec *spec,
                            spec->n_buckets, set->d_pmax, set->d_psum,
                            set->d_pcnt);
         int mb = (spec->n_buckets + 3) / 4;
-        hipLaunchKernelGGL(k_agg_merge, dim3(mb > 2048 ? 2048 : mb), dim3(256),
+        hipLaunchKernelGGL(k_agg_merge, dim3(grid_items(mb, 2048)), dim3(256),
                            0, ctx->stream, nsg, spec->n_buckets, set->d_pmax,
                            set->d_psum, set->d_pcnt, spec->d_agg_max,
                            spec->d_agg_sum, spec->d_agg_count);
@@ -5215,12 +5253,12 @@ GsStatus cm_plan_ranks(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
     a.counts = d_counts;
     a.out_off = d_ooff;
 
-    pl.gx = nseries > 2048 ? 2048 : nseries;
+    pl.gx = grid_items(nseries, 2048);
     hipLaunchKernelGGL(k_cm_flags, dim3(pl.gx, nsets), dim3(256), 0,
                        ctx->stream, a, nsets, nseries, ctx->d_err);
     int total = nsets * nseries;
     hipLaunchKernelGGL(k_cm_prefix,
-                       dim3(total > 65535 ? 65535 : total), dim3(256), 0,
+                       dim3(grid_items(total, 65535)), dim3(256), 0,
                        ctx->stream, a, nsets, nseries);
     std::vector<int64_t> counts(size_t(nsets) * nseries);
     pl.ooff.assign(size_t(nseries) + 1, 0);

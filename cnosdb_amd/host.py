@@ -6,6 +6,7 @@ stands, `Engine.decode` standing where `decode_pages` stands
 (tskv/src/tsm/reader.rs:494-560), `Engine.scan` standing where the
 pure-time-range `DataFilter` + downsampling aggregate stand.
 """
+import contextlib
 import ctypes
 import os
 
@@ -206,6 +207,10 @@ class PageLib:
             ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
             ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+        lib.gs_debug_set_grid_cap.restype = ctypes.c_int32
+        lib.gs_debug_set_grid_cap.argtypes = [ctypes.c_int32]
+        lib.gs_debug_grid_rounds.restype = ctypes.c_int32
+        lib.gs_debug_grid_rounds.argtypes = [ctypes.c_int]
 
     def err(self):
         return self.lib.gs_last_error().decode()
@@ -933,3 +938,24 @@ def scan_fields_async(engine, gset, fields, d_ts, d_val, time_range,
     if st != 0:
         raise RuntimeError(
             f"gs_scan_fields_async failed ({st}): {engine._pl.err()}")
+
+
+def grid_rounds(reset=False):
+    """Largest ceil(uncapped blocks / granted blocks) of any capped launch
+    since the last reset (gs_debug_grid_rounds)."""
+    return int(PageLib().lib.gs_debug_grid_rounds(1 if reset else 0))
+
+
+@contextlib.contextmanager
+def grid_cap(max_blocks):
+    """Test seam: cap every capped kernel launch at max_blocks blocks
+    (gs_debug_set_grid_cap), so a small set drives the kernels through
+    several trips of their grid-stride loops.  Resets the round counter on
+    entry and restores the previous cap on exit, whatever happens inside."""
+    lib = PageLib().lib
+    prev = lib.gs_debug_set_grid_cap(int(max_blocks))
+    lib.gs_debug_grid_rounds(1)
+    try:
+        yield
+    finally:
+        lib.gs_debug_set_grid_cap(prev)
