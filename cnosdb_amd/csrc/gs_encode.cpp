@@ -46,7 +46,7 @@ int64_t gs_encode_i64(const int64_t *src, size_t n, uint8_t *dst, size_t cap) {
 int64_t gs_encode_f64(const double *src, size_t n, uint8_t *dst, size_t cap) {
     if (n == 0) return 0;
     if (cap < tsm_gorilla_max_len(n)) return GS_ERR_CAP;
-    return host_code(tsm_enc_gorilla(src, nullptr, n, dst));
+    return host_code(tsm_enc_gorilla(src, n, dst));
 }
 
 int64_t gs_encode_bool(const uint8_t *src, size_t n, uint8_t *dst, size_t cap) {

@@ -1667,8 +1667,6 @@ __global__ void k_str_gather(const uint8_t *__restrict__ scratch,
 
 struct CompactArgs {
     const int64_t *ts[GS_MAX_STREAMS];
-    const double *val[GS_MAX_STREAMS];
-    const uint8_t *valid[GS_MAX_STREAMS];
     const DevGroup *groups[GS_MAX_STREAMS];
     uint8_t *flags[GS_MAX_STREAMS];
     int32_t *prefix[GS_MAX_STREAMS];
@@ -1698,6 +1696,44 @@ __device__ __forceinline__ bool dev_ts_contains(const int64_t *t, int64_t n,
  * diverge across a __syncthreads). */
 #define CM_TILE 2048 /* stream-f elements per tile (8 per lane; 1024 and 4096 measured slower) */
 #define CM_W 2048    /* LDS window entries (16 KiB) per chunk */
+
+/* Window [wl, wend) of the n2 > 0 sorted rows of t2 that can equal a tile
+ * value in [x_lo, x_hi]: thread 0 bisects into wb_sh, the block reads it
+ * between two barriers (the second frees wb_sh for the next search). */
+__device__ __forceinline__ void cm_window(const int64_t *t2, int64_t n2,
+                                          int64_t x_lo, int64_t x_hi,
+                                          int64_t *wb_sh, int64_t &wl,
+                                          int64_t &wend) {
+    if (threadIdx.x == 0) {
+        int64_t lo = 0, hi = n2;
+        while (lo < hi) {
+            int64_t m = (lo + hi) >> 1;
+            if (t2[m] < x_lo) lo = m + 1; else hi = m;
+        }
+        wb_sh[0] = lo;
+        int64_t lo2 = lo, hi2 = n2;
+        while (lo2 < hi2) {
+            int64_t m = (lo2 + hi2) >> 1;
+            if (t2[m] <= x_hi) lo2 = m + 1; else hi2 = m;
+        }
+        wb_sh[1] = lo2;
+    }
+    __syncthreads();
+    wl = wb_sh[0];
+    wend = wb_sh[1];
+    __syncthreads();
+}
+
+/* first i in [0, wcnt] with wts[i] >= x, over the LDS window */
+__device__ __forceinline__ int cm_lower_bound(const int64_t *wts, int wcnt,
+                                              int64_t x) {
+    int lo = 0, hi = wcnt;
+    while (lo < hi) {
+        int m = (lo + hi) >> 1;
+        if (wts[m] < x) lo = m + 1; else hi = m;
+    }
+    return lo;
+}
 
 __global__ void k_cm_flags(CompactArgs a, int nsets, int nseries,
                            unsigned *__restrict__ err) {
@@ -1730,24 +1766,8 @@ __global__ void k_cm_flags(CompactArgs a, int nsets, int nseries,
                 const int64_t *t2 = a.ts[f2] + g2.row_off;
                 const int64_t n2 = g2.nrows;
                 if (n2 == 0) continue;
-                /* window [wl, wh) = rows of t2 that can equal a tile x */
-                if (threadIdx.x == 0) {
-                    int64_t lo = 0, hi = n2;
-                    while (lo < hi) {
-                        int64_t m = (lo + hi) >> 1;
-                        if (t2[m] < x_lo) lo = m + 1; else hi = m;
-                    }
-                    wb_sh[0] = lo;
-                    int64_t lo2 = lo, hi2 = n2;
-                    while (lo2 < hi2) {
-                        int64_t m = (lo2 + hi2) >> 1;
-                        if (t2[m] <= x_hi) lo2 = m + 1; else hi2 = m;
-                    }
-                    wb_sh[1] = lo2;
-                }
-                __syncthreads();
-                const int64_t wl = wb_sh[0], wend = wb_sh[1];
-                __syncthreads();
+                int64_t wl, wend;
+                cm_window(t2, n2, x_lo, x_hi, wb_sh, wl, wend);
                 int k = 0; /* this lane's next unresolved element */
                 for (int64_t wbase = wl; wbase < wend; wbase += CM_W) {
                     const int wcnt = int(wend - wbase < CM_W ? wend - wbase
@@ -1758,11 +1778,7 @@ __global__ void k_cm_flags(CompactArgs a, int nsets, int nseries,
                     const int64_t w_last = wts[wcnt - 1];
                     const bool last_chunk = wbase + wcnt == wend;
                     while (k < ne && (x[k] <= w_last || last_chunk)) {
-                        int lo = 0, hi = wcnt; /* LDS lower bound */
-                        while (lo < hi) {
-                            int m = (lo + hi) >> 1;
-                            if (wts[m] < x[k]) lo = m + 1; else hi = m;
-                        }
+                        const int lo = cm_lower_bound(wts, wcnt, x[k]);
                         if (lo < wcnt && wts[lo] == x[k]) own[k] = false;
                         k++;
                     }
@@ -1821,136 +1837,8 @@ __global__ void k_cm_prefix(CompactArgs a, int nsets, int nseries) {
     }
 }
 
-/* block per (set, series): scatter owners to merged positions with
- * newest-non-null value selection */
-/* LDS-staged tiled scatter (see k_cm_flags): the merged position (rank
- * over all streams) and the dedup value come from the same LDS windows.
- * The dedup walk is folded into a DESCENDING stream pass: the newest
- * non-null among {f, older hits} wins (batch_builder.rs:106-155), so the
- * first hit with a valid value while walking f-1, f-2, ... resolves it
- * without a per-element hit array. */
-__global__ void k_cm_scatter(CompactArgs a, int nsets, int nseries,
-                             int64_t *__restrict__ out_ts,
-                             double *__restrict__ out_val,
-                             uint8_t *__restrict__ out_valid) {
-    __shared__ int64_t wts[CM_W];
-    __shared__ int32_t wpf[CM_W]; /* prefix window: the per-owner rank adds
-                                     were ~645M scattered 4/1-B global
-                                     loads — staged once, coalesced */
-    __shared__ uint8_t wfl[CM_W];
-    __shared__ int64_t wb_sh[2];
-    int f = blockIdx.y;
-    for (int s = blockIdx.x; s < nseries; s += gridDim.x) {
-        DevGroup g = a.groups[f][s];
-        const int64_t *t = a.ts[f] + g.row_off;
-        const uint8_t *fl = a.flags[f] + g.row_off;
-        const int32_t *pf = a.prefix[f] + g.row_off;
-        const uint8_t *vdf = a.valid[f];
-        const int64_t base = a.out_off[s];
-        for (int64_t j0 = 0; j0 < g.nrows; j0 += CM_TILE) {
-            const int64_t je = j0 + CM_TILE < g.nrows ? j0 + CM_TILE
-                                                      : g.nrows;
-            int64_t x[CM_TILE / 256];
-            int64_t pos[CM_TILE / 256];
-            double v[CM_TILE / 256];
-            bool own[CM_TILE / 256], okv[CM_TILE / 256];
-            int ne = 0;
-            for (int64_t j = j0 + threadIdx.x; j < je; j += blockDim.x) {
-                x[ne] = t[j];
-                own[ne] = fl[j] != 0;
-                pos[ne] = base + pf[j];
-                const int64_t row = g.row_off + j;
-                const bool o = !vdf || vdf[row];
-                v[ne] = o ? a.val[f][row] : 0.0;
-                okv[ne] = o;
-                ne++;
-            }
-            const int64_t x_lo = t[j0], x_hi = t[je - 1];
-            /* descending pass: newer streams contribute rank only; older
-               streams contribute rank + the first valid dedup value */
-            for (int f2 = nsets - 1; f2 >= 0; f2--) {
-                if (f2 == f) continue;
-                DevGroup g2 = a.groups[f2][s];
-                const int64_t *t2 = a.ts[f2] + g2.row_off;
-                const int32_t *pf2 = a.prefix[f2] + g2.row_off;
-                const uint8_t *fl2 = a.flags[f2] + g2.row_off;
-                const int64_t n2 = g2.nrows;
-                if (n2 == 0) continue;
-                if (threadIdx.x == 0) {
-                    int64_t lo = 0, hi = n2;
-                    while (lo < hi) {
-                        int64_t m = (lo + hi) >> 1;
-                        if (t2[m] < x_lo) lo = m + 1; else hi = m;
-                    }
-                    wb_sh[0] = lo;
-                    int64_t lo2 = lo, hi2 = n2;
-                    while (lo2 < hi2) {
-                        int64_t m = (lo2 + hi2) >> 1;
-                        if (t2[m] <= x_hi) lo2 = m + 1; else hi2 = m;
-                    }
-                    wb_sh[1] = lo2;
-                }
-                __syncthreads();
-                const int64_t wl = wb_sh[0], wend = wb_sh[1];
-                __syncthreads();
-                if (wl == wend) { /* tile range absent from t2: rank only */
-                    if (wl > 0)
-                        for (int i = 0; i < ne; i++)
-                            if (own[i])
-                                pos[i] += pf2[wl - 1] + fl2[wl - 1];
-                    continue;
-                }
-                int k = 0;
-                for (int64_t wbase = wl; wbase < wend; wbase += CM_W) {
-                    const int wcnt = int(wend - wbase < CM_W ? wend - wbase
-                                                             : CM_W);
-                    for (int i = threadIdx.x; i < wcnt; i += blockDim.x) {
-                        wts[i] = t2[wbase + i];
-                        wpf[i] = pf2[wbase + i];
-                        wfl[i] = fl2[wbase + i];
-                    }
-                    __syncthreads();
-                    const int64_t w_last = wts[wcnt - 1];
-                    const bool last_chunk = wbase + wcnt == wend;
-                    while (k < ne && (x[k] <= w_last || last_chunk)) {
-                        if (own[k]) {
-                            int lo = 0, hi = wcnt; /* LDS lower bound */
-                            while (lo < hi) {
-                                int m = (lo + hi) >> 1;
-                                if (wts[m] < x[k]) lo = m + 1; else hi = m;
-                            }
-                            const int64_t p2 = wbase + lo;
-                            if (lo > 0)
-                                pos[k] += wpf[lo - 1] + wfl[lo - 1];
-                            else if (p2 > 0)
-                                pos[k] += pf2[p2 - 1] + fl2[p2 - 1];
-                            if (f2 < f && !okv[k] && lo < wcnt &&
-                                wts[lo] == x[k]) {
-                                const int64_t row2 = g2.row_off + p2;
-                                const uint8_t *vd2 = a.valid[f2];
-                                if (!vd2 || vd2[row2]) {
-                                    v[k] = a.val[f2][row2];
-                                    okv[k] = true;
-                                }
-                            }
-                        }
-                        k++;
-                    }
-                    __syncthreads();
-                }
-            }
-            for (int i = 0; i < ne; i++) {
-                if (!own[i]) continue;
-                out_ts[pos[i]] = x[i];
-                out_val[pos[i]] = okv[i] ? v[i] : 0.0;
-                if (out_valid) out_valid[pos[i]] = okv[i];
-            }
-            __syncthreads();
-        }
-    }
-}
-
-/* ---- multi-column scatter (gs_compact_merge_fields) ----
+/* ---- scatter (gs_compact_merge_fields; gs_compact_merge is its
+ * one-column case) ----
  * A column group is a time column plus every field column of the table;
  * BatchMergeBuilder::take_last_and_merge (batch_builder.rs:132-155)
  * resolves each column independently over the rows sharing a timestamp:
@@ -1963,7 +1851,7 @@ __global__ void k_cm_scatter(CompactArgs a, int nsets, int nseries,
  *   val[f*ncols+c], valid[f*ncols+c]  (NULL val = column absent in f,
  *   NULL valid = all rows valid), out_val[c], out_valid[c]. */
 struct CompactFieldsArgs {
-    CompactArgs m;               /* val/valid unused here */
+    CompactArgs m;
     const void *const *val;      /* device [nsets*ncols] */
     const uint8_t *const *valid; /* device [nsets*ncols] */
     void *const *out_val;        /* device [ncols] */
@@ -1982,8 +1870,9 @@ __device__ __forceinline__ void cm_move_cell(void *dst, int64_t dpos,
         ((uint8_t *)dst)[dpos] = ((const uint8_t *)src)[srow];
 }
 
-/* Same tiling as k_cm_scatter (CM_TILE stream-f elements, 8 per lane; the
- * window of every other stream staged once in LDS).  A lane cannot hold
+/* Same tiling as k_cm_flags (CM_TILE stream-f elements, 8 per lane; the
+ * window of every other stream staged once in LDS, with its prefix and
+ * flag windows, so the rank adds are LDS reads too).  A lane cannot hold
  * ncols x 8 pending values, so values resolve against the final position:
  *   1. rank pass over all other streams -> pos; older-stream hits are
  *      kept as a 16-bit mask per element
@@ -1996,8 +1885,8 @@ __device__ __forceinline__ void cm_move_cell(void *dst, int64_t dpos,
  *   4. leftovers get the zero value and validity 0.
  * Every output cell is stored exactly once, in a fixed order, with plain
  * stores.  Per-lane arrays are only ever indexed by unrolled constants
- * (a done-mask replaces k_cm_scatter's running index), so they stay in
- * VGPRs: no scratch. */
+ * (a done-mask, not a running index, tracks a lane's progress), so they
+ * stay in VGPRs: no scratch. */
 __global__ void __launch_bounds__(256)
 k_cm_scatter_fields(CompactFieldsArgs a, int nsets, int nseries,
                     int64_t *__restrict__ out_ts) {
@@ -2045,23 +1934,8 @@ k_cm_scatter_fields(CompactFieldsArgs a, int nsets, int nseries,
                 const uint8_t *fl2 = a.m.flags[f2] + g2.row_off;
                 const int64_t n2 = g2.nrows;
                 if (n2 == 0) continue;
-                if (threadIdx.x == 0) {
-                    int64_t lo = 0, hi = n2;
-                    while (lo < hi) {
-                        int64_t m = (lo + hi) >> 1;
-                        if (t2[m] < x_lo) lo = m + 1; else hi = m;
-                    }
-                    wb_sh[0] = lo;
-                    int64_t lo2 = lo, hi2 = n2;
-                    while (lo2 < hi2) {
-                        int64_t m = (lo2 + hi2) >> 1;
-                        if (t2[m] <= x_hi) lo2 = m + 1; else hi2 = m;
-                    }
-                    wb_sh[1] = lo2;
-                }
-                __syncthreads();
-                const int64_t wl = wb_sh[0], wend = wb_sh[1];
-                __syncthreads();
+                int64_t wl, wend;
+                cm_window(t2, n2, x_lo, x_hi, wb_sh, wl, wend);
                 if (wl == wend) { /* tile range absent from t2: rank only */
                     if (wl > 0) {
                         const int64_t add = pf2[wl - 1] + fl2[wl - 1];
@@ -2089,11 +1963,7 @@ k_cm_scatter_fields(CompactFieldsArgs a, int nsets, int nseries,
                             !(x[i] <= w_last || last_chunk))
                             continue;
                         todo &= ~(1u << i);
-                        int lo = 0, hi = wcnt; /* LDS lower bound */
-                        while (lo < hi) {
-                            int m = (lo + hi) >> 1;
-                            if (wts[m] < x[i]) lo = m + 1; else hi = m;
-                        }
+                        const int lo = cm_lower_bound(wts, wcnt, x[i]);
                         const int64_t p2 = wbase + lo;
                         if (lo > 0)
                             pos[i] += wpf[lo - 1] + wfl[lo - 1];
@@ -2145,23 +2015,8 @@ k_cm_scatter_fields(CompactFieldsArgs a, int nsets, int nseries,
                     const DevGroup g2 = a.m.groups[f2][s];
                     const int64_t *t2 = a.m.ts[f2] + g2.row_off;
                     const int64_t n2 = g2.nrows;
-                    if (threadIdx.x == 0) {
-                        int64_t lo = 0, hi = n2;
-                        while (lo < hi) {
-                            int64_t m = (lo + hi) >> 1;
-                            if (t2[m] < x_lo) lo = m + 1; else hi = m;
-                        }
-                        wb_sh[0] = lo;
-                        int64_t lo2 = lo, hi2 = n2;
-                        while (lo2 < hi2) {
-                            int64_t m = (lo2 + hi2) >> 1;
-                            if (t2[m] <= x_hi) lo2 = m + 1; else hi2 = m;
-                        }
-                        wb_sh[1] = lo2;
-                    }
-                    __syncthreads();
-                    const int64_t wl = wb_sh[0], wend = wb_sh[1];
-                    __syncthreads();
+                    int64_t wl, wend;
+                    cm_window(t2, n2, x_lo, x_hi, wb_sh, wl, wend);
                     uint32_t todo = 0;
 #pragma unroll
                     for (int i = 0; i < NE; i++)
@@ -2180,11 +2035,7 @@ k_cm_scatter_fields(CompactFieldsArgs a, int nsets, int nseries,
                                 !(x[i] <= w_last || last_chunk))
                                 continue;
                             todo &= ~(1u << i);
-                            int lo = 0, hi = wcnt;
-                            while (lo < hi) {
-                                int m = (lo + hi) >> 1;
-                                if (wts[m] < x[i]) lo = m + 1; else hi = m;
-                            }
+                            const int lo = cm_lower_bound(wts, wcnt, x[i]);
                             if (lo >= wcnt || wts[lo] != x[i]) continue;
                             const int64_t row2 = g2.row_off + wbase + lo;
                             for (int c = 0; c < ncols; c++) {
@@ -2970,9 +2821,8 @@ __global__ void k_agg_fixup(const DevAggMeta *__restrict__ pc_meta,
  * Page::arrow_array_to_page, tsm/page.rs:100-353): one thread per output
  * page running the encoders of gs_tsm_enc.h, the functions the host entry
  * points of gs_encode.cpp run (pinned by the reference's golden vectors).
- * The ts/i64 encoder is multi-pass and wants all-valid input (time columns
- * are never null; k_enc_prepare densifies i64 columns first); Gorilla
- * streams past nulls inline. */
+ * The encoders want all-valid input (time columns are never null;
+ * k_enc_prepare densifies every null-carrying column first). */
 
 struct EncPageSpec {
     int64_t row_off;
@@ -3002,54 +2852,9 @@ __device__ __forceinline__ int64_t enc_seal_page(
     return 16 + int64_t(bl) + dl;
 }
 
-/* one thread per output page: bitset + encode + seal */
-__global__ void k_encode_pages(int kind /*0=ts 1=i64 2=f64*/,
-                               const void *__restrict__ vals,
-                               const uint8_t *__restrict__ valid,
-                               const EncPageSpec *__restrict__ pages,
-                               int npages, uint8_t *__restrict__ out,
-                               int64_t cap, int64_t *__restrict__ lens,
-                               unsigned *__restrict__ err) {
-    __shared__ uint32_t crct[256];
-    enc_crc_table(crct);
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npages;
-         p += gridDim.x * blockDim.x) {
-        EncPageSpec ps = pages[p];
-        uint8_t *pg = out + int64_t(p) * cap;
-        uint32_t bl = uint32_t(ps.nrows + 7) / 8;
-        /* validity bitset, LSB-first */
-        uint8_t *bs = pg + 16;
-        for (uint32_t b = 0; b < bl; b++) {
-            uint8_t byte = 0;
-            for (int k = 0; k < 8; k++) {
-                int32_t r = int32_t(b) * 8 + k;
-                if (r < ps.nrows && (!valid || valid[ps.row_off + r]))
-                    byte |= uint8_t(1u << k);
-            }
-            bs[b] = byte;
-        }
-        uint8_t *data = pg + 16 + bl;
-        const size_t n = ps.nrows > 0 ? size_t(ps.nrows) : 0;
-        int64_t dl;
-        if (kind == 2) {
-            dl = tsm_enc_gorilla((const double *)vals + ps.row_off,
-                                 valid ? valid + ps.row_off : nullptr, n, data);
-        } else {
-            if (valid) { /* int encoders need all-valid input (see header) */
-                bool av = true;
-                for (int32_t r = 0; r < ps.nrows; r++)
-                    if (!valid[ps.row_off + r]) { av = false; break; }
-                if (!av) { atomicOr(err, DERR_ENC_NULL); lens[p] = -3; continue; }
-            }
-            dl = tsm_enc_int(kind == 0, (const int64_t *)vals + ps.row_off, n,
-                             data, nullptr);
-        }
-        lens[p] = enc_seal_page(pg, bl, ps.nrows, data, dl, crct, err);
-    }
-}
-
-/* ---- column-group re-encode (gs_encode_group_pages_dev): every page of
- * every column of a merged column group in two launches.  k_enc_prepare
+/* ---- column-group re-encode (gs_encode_group_pages_dev, and
+ * gs_encode_pages_dev as its one-column case): every page of every column
+ * of a merged column group in two launches.  k_enc_prepare
  * does the per-page work that parallelises (bitset, null densification,
  * count, statistics, bool packing), one block per (column, page);
  * k_enc_group_pages then runs the serial int/Gorilla encoders over
@@ -3064,8 +2869,9 @@ struct EncGroupCol {
     uint8_t *out;
     int64_t cap;
     int32_t ctype;
-    int32_t pad;
+    uint32_t flags;
 };
+#define ENC_COL_NO_NULLS 1u /* a null row fails the page, as in a time column */
 
 #define ENC_PREP_THREADS 256
 #define ENC_PREP_WAVES (ENC_PREP_THREADS / 64)
@@ -3225,7 +3031,7 @@ __global__ __launch_bounds__(ENC_PREP_THREADS) void k_enc_prepare(
 }
 
 /* one thread per (column, page): encode the dense values and seal the
- * page, as k_encode_pages does */
+ * page */
 __global__ void k_enc_group_pages(const EncGroupCol *__restrict__ cols,
                                   int ncols,
                                   const EncPageSpec *__restrict__ pages,
@@ -3244,7 +3050,8 @@ __global__ void k_enc_group_pages(const EncGroupCol *__restrict__ cols,
         const uint32_t bl = uint32_t(ps.nrows + 7) / 8;
         uint8_t *data = pg + 16 + bl;
         const int32_t nn = cnt[w];
-        if (col.ctype == GS_CT_TIME && nn != ps.nrows) {
+        if ((col.ctype == GS_CT_TIME || (col.flags & ENC_COL_NO_NULLS)) &&
+            nn != ps.nrows) {
             atomicOr(err, DERR_ENC_NULL); /* the time column is never null */
             info[w].len = -3;
             continue;
@@ -3252,8 +3059,8 @@ __global__ void k_enc_group_pages(const EncGroupCol *__restrict__ cols,
         const void *src = col.dense ? col.dense : col.vals;
         int64_t dl;
         if (col.ctype == GS_CT_F64)
-            dl = tsm_enc_gorilla((const double *)src + ps.row_off, nullptr,
-                                 size_t(nn), data);
+            dl = tsm_enc_gorilla((const double *)src + ps.row_off, size_t(nn),
+                                 data);
         else if (col.ctype == GS_CT_BOOL) /* packed by k_enc_prepare */
             dl = int64_t(tsm_bool_len(uint64_t(nn)));
         else /* u64 is the i64 codec over the same bits (unsigned.rs:15-18) */
@@ -5047,59 +4854,19 @@ static GsStatus enc_dev_status(GsCtx *ctx, const char *null_row_msg) {
     return fail(GS_ERR_FORMAT, "encode: value out of simple8b range");
 }
 
-GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
-                             const uint8_t *d_valid, const int64_t *h_row_off,
-                             const int32_t *h_rows, int32_t npages,
-                             uint8_t *d_out, int64_t cap_per_page,
-                             int64_t *h_lens) {
-    if (!ctx || !d_vals || !h_row_off || !h_rows || npages <= 0 || !d_out ||
-        !h_lens || kind < 0 || kind > 2)
-        return fail(GS_ERR, "bad args to gs_encode_pages_dev");
-    int32_t maxr = 0;
-    for (int32_t p = 0; p < npages; p++) if (h_rows[p] > maxr) maxr = h_rows[p];
-    /* worst case: ints -> uncompressed 8 B/val; f64 -> ~77 bits/val */
-    int64_t need = 16 + (int64_t(maxr) + 7) / 8 + enc_dev_max_len(kind == 2, maxr);
-    if (cap_per_page < need)
-        return fail(GS_ERR_CAP, "cap_per_page below worst-case encoded size");
-    HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<EncPageSpec> specs(npages);
-    for (int32_t p = 0; p < npages; p++) {
-        specs[p].row_off = h_row_off[p];
-        specs[p].nrows = h_rows[p];
-        specs[p].pad = 0;
-    }
-    EncPageSpec *d_specs;
-    int64_t *d_lens;
-    HIP_TRY(hipMalloc(&d_specs, size_t(npages) * sizeof(EncPageSpec)));
-    if (hipMalloc(&d_lens, size_t(npages) * 8) != hipSuccess) {
-        hipFree(d_specs);
-        return fail(GS_ERR, "hipMalloc lens failed");
-    }
-    hipMemcpyAsync(d_specs, specs.data(), size_t(npages) * sizeof(EncPageSpec),
-                   hipMemcpyHostToDevice, ctx->stream);
-    hipLaunchKernelGGL(k_encode_pages, dim3(grid_for(npages, 256)), dim3(256),
-                       0, ctx->stream, kind, d_vals, d_valid, d_specs, npages,
-                       d_out, cap_per_page, d_lens, ctx->d_err);
-    GsStatus st = GS_OK;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess)
-        st = fail(GS_ERR, "encode kernel failed");
-    hipMemcpy(h_lens, d_lens, size_t(npages) * 8, hipMemcpyDeviceToHost);
-    hipFree(d_specs);
-    hipFree(d_lens);
-    if (st != GS_OK) return st;
-    return enc_dev_status(ctx, "encode: null row in a ts/i64 page (integer "
-                               "pages must be all-valid)");
-}
-
-GsStatus gs_encode_group_pages_dev(GsCtx *ctx, int32_t ncols,
-                                   const uint8_t *ctype,
-                                   const void *const *d_vals,
-                                   const uint8_t *const *d_valid,
-                                   const int64_t *h_row_off,
-                                   const int32_t *h_rows, int32_t npages,
-                                   uint8_t *const *d_out,
-                                   const int64_t *cap_per_page,
-                                   GsPageInfo *h_info) {
+/* Both encode entries.  no_nulls: every column refuses a page with a null
+ * row, as the time column always does; null_row_msg is that refusal's
+ * message. */
+static GsStatus enc_group_pages(GsCtx *ctx, int32_t ncols,
+                                const uint8_t *ctype,
+                                const void *const *d_vals,
+                                const uint8_t *const *d_valid,
+                                const int64_t *h_row_off,
+                                const int32_t *h_rows, int32_t npages,
+                                uint8_t *const *d_out,
+                                const int64_t *cap_per_page,
+                                GsPageInfo *h_info, bool no_nulls,
+                                const char *null_row_msg) {
     if (ncols < 1 || ncols > GS_MAX_ENCODE_COLS)
         return fail(GS_ERR, "gs_encode_group_pages_dev: ncols outside "
                             "1..GS_MAX_ENCODE_COLS");
@@ -5157,7 +4924,7 @@ GsStatus gs_encode_group_pages_dev(GsCtx *ctx, int32_t ncols,
         cols[c].out = d_out[c];
         cols[c].cap = cap_per_page[c];
         cols[c].ctype = ctype[c];
-        cols[c].pad = 0;
+        cols[c].flags = no_nulls ? ENC_COL_NO_NULLS : 0;
         if (cols[c].valid) { /* only null-carrying columns are densified */
             cols[c].dense =
                 dalloc(size_t(extent) * (ctype[c] == GS_CT_BOOL ? 1 : 8));
@@ -5201,14 +4968,50 @@ GsStatus gs_encode_group_pages_dev(GsCtx *ctx, int32_t ncols,
         st = fail(GS_ERR, "group encode: page info readback failed");
     release();
     if (st != GS_OK) return st;
-    return enc_dev_status(ctx, "encode: null row in the time column");
+    return enc_dev_status(ctx, null_row_msg);
 }
 
-/* Host-side setup shared by both merge entries: everything that depends
+GsStatus gs_encode_group_pages_dev(GsCtx *ctx, int32_t ncols,
+                                   const uint8_t *ctype,
+                                   const void *const *d_vals,
+                                   const uint8_t *const *d_valid,
+                                   const int64_t *h_row_off,
+                                   const int32_t *h_rows, int32_t npages,
+                                   uint8_t *const *d_out,
+                                   const int64_t *cap_per_page,
+                                   GsPageInfo *h_info) {
+    return enc_group_pages(ctx, ncols, ctype, d_vals, d_valid, h_row_off,
+                           h_rows, npages, d_out, cap_per_page, h_info, false,
+                           "encode: null row in the time column");
+}
+
+/* one column of the group encode; the statistics are dropped */
+GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
+                             const uint8_t *d_valid, const int64_t *h_row_off,
+                             const int32_t *h_rows, int32_t npages,
+                             uint8_t *d_out, int64_t cap_per_page,
+                             int64_t *h_lens) {
+    if (!ctx || !d_vals || !h_row_off || !h_rows || npages <= 0 || !d_out ||
+        !h_lens || kind < 0 || kind > 2)
+        return fail(GS_ERR, "bad args to gs_encode_pages_dev");
+    const uint8_t ctype =
+        kind == 0 ? GS_CT_TIME : kind == 1 ? GS_CT_I64 : GS_CT_F64;
+    std::vector<GsPageInfo> info(npages);
+    GsStatus st = enc_group_pages(
+        ctx, 1, &ctype, &d_vals, &d_valid, h_row_off, h_rows, npages, &d_out,
+        &cap_per_page, info.data(), kind == 1,
+        "encode: null row in a ts/i64 page (integer pages must be all-valid)");
+    /* with these three the launch ran and every page has its length */
+    if (st == GS_OK || st == GS_ERR_FORMAT || st == GS_ERR_SENTINEL)
+        for (int32_t p = 0; p < npages; p++) h_lens[p] = info[p].len;
+    return st;
+}
+
+/* Host-side setup of the merge: everything that depends
  * on the timestamps only.  Allocates the per-stream flag/prefix scratch,
  * runs k_cm_flags + k_cm_prefix once, and turns the per-(stream, series)
  * owner counts into per-series output offsets (host copy in ooff, device
- * copy enqueued on the ctx stream).  The caller launches its scatter
+ * copy enqueued on the ctx stream).  The caller launches the scatter
  * kernel, synchronizes, and frees plan.scratch. */
 namespace {
 struct CmPlan {
@@ -5276,43 +5079,6 @@ GsStatus cm_plan_ranks(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
     return GS_OK;
 }
 } // namespace
-
-GsStatus gs_compact_merge(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
-                          const int64_t *const *d_ts,
-                          const double *const *d_val,
-                          const uint8_t *const *d_valid, int64_t *d_out_ts,
-                          double *d_out_val, uint8_t *d_out_valid,
-                          int64_t *h_out_offsets, int64_t *out_rows) {
-    if (!ctx || !sets || nsets < 1 || nsets > GS_MAX_STREAMS || !d_ts ||
-        !d_val || !d_out_ts || !d_out_val)
-        return fail(GS_ERR, "bad args to gs_compact_merge");
-    int nseries = sets[0]->nsgroups;
-    for (int f = 0; f < nsets; f++)
-        if (sets[f]->nsgroups != nseries)
-            return fail(GS_ERR, "all streams must cover the same series list");
-    HIP_TRY(hipSetDevice(ctx->device));
-
-    CmPlan pl;
-    pl.nseries = nseries;
-    GsStatus st = cm_plan_ranks(ctx, sets, nsets, d_ts, pl);
-    if (st != GS_OK) { pl.release(); return st; }
-    for (int f = 0; f < nsets; f++) {
-        pl.a.val[f] = d_val[f];
-        pl.a.valid[f] = d_valid ? d_valid[f] : nullptr;
-    }
-    hipLaunchKernelGGL(k_cm_scatter, dim3(pl.gx, nsets), dim3(256), 0,
-                       ctx->stream, pl.a, nsets, nseries, d_out_ts, d_out_val,
-                       d_out_valid);
-    hipError_t he = hipStreamSynchronize(ctx->stream);
-    pl.release();
-    HIP_TRY(he);
-    st = check_dev_err(ctx);
-    if (st != GS_OK) return st;
-    if (h_out_offsets)
-        memcpy(h_out_offsets, pl.ooff.data(), size_t(nseries + 1) * 8);
-    if (out_rows) *out_rows = pl.ooff[nseries];
-    return GS_OK;
-}
 
 GsStatus gs_compact_merge_fields(GsCtx *ctx, GsGroupSet *const *sets,
                                  int32_t nsets, int32_t ncols,
@@ -5402,6 +5168,26 @@ GsStatus gs_compact_merge_fields(GsCtx *ctx, GsGroupSet *const *sets,
         memcpy(h_out_offsets, pl.ooff.data(), size_t(nseries + 1) * 8);
     if (out_rows) *out_rows = pl.ooff[nseries];
     return GS_OK;
+}
+
+/* the one-column case of gs_compact_merge_fields: the per-stream d_val and
+ * d_valid arrays are its [nsets*1] tables */
+GsStatus gs_compact_merge(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
+                          const int64_t *const *d_ts,
+                          const double *const *d_val,
+                          const uint8_t *const *d_valid, int64_t *d_out_ts,
+                          double *d_out_val, uint8_t *d_out_valid,
+                          int64_t *h_out_offsets, int64_t *out_rows) {
+    if (!ctx || !sets || nsets < 1 || nsets > GS_MAX_STREAMS || !d_ts ||
+        !d_val || !d_out_ts || !d_out_val)
+        return fail(GS_ERR, "bad args to gs_compact_merge");
+    const int32_t elem_size = 8;
+    void *const out_val = d_out_val;
+    uint8_t *const out_valid = d_out_valid;
+    return gs_compact_merge_fields(ctx, sets, nsets, 1, &elem_size, d_ts,
+                                   (const void *const *)d_val, d_valid,
+                                   d_out_ts, &out_val, &out_valid,
+                                   h_out_offsets, out_rows);
 }
 
 /* ---- Arrow C Data Interface export ---- */

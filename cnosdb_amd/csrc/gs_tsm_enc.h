@@ -1,8 +1,8 @@
 /* The TSM DataBlock encoders and the page header: the single home of the
  * write-side codecs.  The host entry points of gs_encode.cpp and the device
- * kernels k_encode_pages / k_enc_prepare / k_enc_group_pages of
- * gs_engine.cpp all go through the functions below, so a page encoded on the
- * host and one encoded on the device are the same code's output.
+ * kernels k_enc_prepare / k_enc_group_pages of gs_engine.cpp all go through
+ * the functions below, so a page encoded on the host and one encoded on the
+ * device are the same code's output.
  *
  * Block layouts (reference: tskv/src/tsm/codec/; pinned by the InfluxDB
  * golden blocks, integer.rs:438-483, and the boolean vectors,
@@ -267,21 +267,18 @@ struct TsmBitWriter {
     }
 };
 
-/* Encodes the non-null values of v[0..nrows) (valid: one byte per row, or
- * NULL for all valid) as a Gorilla block of at most tsm_gorilla_max_len of
- * their count; returns its length, 0 when no row is valid, or
- * TSM_ENC_ERR_SENTINEL.  The first non-null value is the header and is not
- * checked against the sentinel. */
-TSM_FN int64_t tsm_enc_gorilla(const double *v, const uint8_t *valid,
-                               size_t nrows, uint8_t *dst) {
+/* Encodes the n values of v, all valid, as a Gorilla block of at most
+ * tsm_gorilla_max_len(n) bytes; returns its length, 0 for n == 0, or
+ * TSM_ENC_ERR_SENTINEL.  The first value is the header and is not checked
+ * against the sentinel. */
+TSM_FN int64_t tsm_enc_gorilla(const double *v, size_t n, uint8_t *dst) {
     auto bits = [&](size_t r) {
         uint64_t b;
         __builtin_memcpy(&b, v + r, 8);
         return b;
     };
+    if (n == 0) return 0;
     size_t r = 0;
-    if (valid) while (r < nrows && !valid[r]) r++;
-    if (r >= nrows) return 0;
     dst[0] = GS_ENC_GORILLA;
     dst[1] = 1 << 4;
     uint64_t prev = bits(r++);
@@ -290,8 +287,7 @@ TSM_FN int64_t tsm_enc_gorilla(const double *v, const uint8_t *valid,
     uint64_t prev_lead = ~0ULL, prev_trail = 0;
     for (;;) {
         uint64_t cur;
-        if (r < nrows) {
-            if (valid && !valid[r]) { r++; continue; }
+        if (r < n) {
             cur = bits(r++);
             if (cur == GORILLA_SENTINEL) return TSM_ENC_ERR_SENTINEL;
         } else {

@@ -306,12 +306,18 @@ GsStatus gs_scan_wait(GsCtx *ctx, GsGroupSet *set, GsScanResult *result);
  * gs_encode_* run on the host, csrc/gs_tsm_enc.h, so it is theirs byte for
  * byte) is written at d_out + p*cap_per_page; h_lens receives encoded
  * lengths.
- * Int encoders (kind 0/1) require all-valid slices — the time column is
- * never null.  Null-carrying i64, u64 and bool columns, and the page
- * statistics, are gs_encode_group_pages_dev's (below), which encodes a
- * whole column group in one call.
+ * This is the one-column case of gs_encode_group_pages_dev (below): the
+ * same kernels with kind 0/1/2 as GS_CT_TIME/I64/F64, the page statistics
+ * dropped.  One thing is this entry's own: kind 0 and kind 1 both require
+ * all-valid slices (the time column is never null, and an i64 page with a
+ * null row is refused here, where the group entry encodes its non-null
+ * values).  Null-carrying i64, u64 and bool columns, and the statistics,
+ * are the group entry's.  A call that passes d_valid holds a dense scratch
+ * column of 8 B per row (up to the last page's end) for its duration.
  *
- * Errors: GS_ERR_CAP (before any device work) when cap_per_page is below
+ * Errors: GS_ERR (before any device work) for a NULL required pointer, a
+ * kind outside 0..2, npages <= 0 or a negative h_rows / h_row_off entry;
+ * GS_ERR_CAP (before any device work) when cap_per_page is below
  * the worst case for the longest page; GS_ERR_SENTINEL when an f64 page
  * holds the Gorilla sentinel as a non-first value, as gs_encode_f64
  * reports it; GS_ERR_FORMAT for a null row in a ts/i64 page.  On the last
@@ -383,7 +389,13 @@ GsStatus gs_encode_group_pages_dev(
  * newest, file_id order) must cover the same series list; d_ts/d_val/
  * d_valid[f] are that stream's decoded columns (from gs_decode).  Outputs
  * are caller device buffers sized >= the sum of input rows;
- * h_out_offsets[nseries+1] receives per-series output row offsets. */
+ * h_out_offsets[nseries+1] receives per-series output row offsets.
+ * d_valid (the array or an entry) and d_out_valid may be NULL; a null
+ * cell's value is zero bits.  This is the one-column case of
+ * gs_compact_merge_fields (below, ncols = 1, elem_size = {8}) and runs the
+ * same kernels.  A stream whose timestamps are not strictly increasing
+ * within a series fails with GS_ERR_FORMAT; the output buffers are then
+ * unspecified. */
 GsStatus gs_compact_merge(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
                           const int64_t *const *d_ts,
                           const double *const *d_val,

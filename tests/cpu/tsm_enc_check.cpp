@@ -14,7 +14,10 @@
  * Every case is encoded into a heap block of exactly the documented worst
  * case (tsm_int_max_len, tsm_gorilla_max_len of the non-null count,
  * tsm_bool_len), so a write past it is an ASan error; the inputs and the
- * packer's scratch sit in exact heap blocks as well.  Length and bytes are
+ * packer's scratch sit in exact heap blocks as well.  An f64 case with
+ * validity bytes is first gathered into an exact block of its non-null
+ * values, in row order: what k_enc_prepare hands the encoder on the
+ * device.  Length and bytes are
  * compared, then the block's CRC and the page header written from it.
  * ts/i64 cases run twice: packing straight from the column, as the device
  * does, and from the scratch array, as the host does. */
@@ -40,12 +43,24 @@ static bool read_exact(FILE *f, void *dst, size_t n) {
     return n == 0 || fread(dst, 1, n, f) == n;
 }
 
+static size_t nonnull(const Case &c) {
+    size_t nn = 0;
+    for (uint32_t r = 0; r < c.nrows; r++) nn += !c.valid || c.valid[r];
+    return nn;
+}
+
 /* one encode of a case; int_scratch picks the int encoder's source */
 static int64_t encode(const Case &c, bool int_scratch, uint8_t *out) {
     const size_t n = c.nrows;
-    if (c.kind == K_F64)
-        return tsm_enc_gorilla((const double *)c.vals.get(), c.valid.get(), n,
-                               out);
+    if (c.kind == K_F64) {
+        const double *v = (const double *)c.vals.get();
+        if (!c.valid) return tsm_enc_gorilla(v, n, out);
+        const size_t nn = nonnull(c);
+        std::unique_ptr<double[]> dense(new double[nn]);
+        for (size_t r = 0, k = 0; r < n; r++)
+            if (c.valid[r]) __builtin_memcpy(&dense[k++], v + r, 8);
+        return tsm_enc_gorilla(dense.get(), nn, out);
+    }
     if (c.kind == K_BOOL) {
         if (n == 0) return 0;
         /* the host's loop; k_enc_prepare gives one j to a thread */
@@ -64,9 +79,7 @@ static int64_t encode(const Case &c, bool int_scratch, uint8_t *out) {
 static size_t worst_case(const Case &c) {
     if (c.kind == K_BOOL) return tsm_bool_len(c.nrows);
     if (c.kind != K_F64) return size_t(tsm_int_max_len(c.nrows));
-    size_t nn = 0;
-    for (uint32_t r = 0; r < c.nrows; r++) nn += !c.valid || c.valid[r];
-    return size_t(tsm_gorilla_max_len(nn));
+    return size_t(tsm_gorilla_max_len(nonnull(c)));
 }
 
 static int check(const Case &c, int ci, bool int_scratch) {

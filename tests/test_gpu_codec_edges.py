@@ -297,12 +297,17 @@ def _pages_out(d_out, cap, lens):
             if lens[p] >= 0 else None for p in range(len(lens))]
 
 
-def _encode(engine, kind, arrays, d_valid=None, cap=None):
+def _encode(engine, kind, arrays, d_valid=None, cap=None, base=0):
     """One gs_encode_pages_dev launch over the concatenation of arrays,
-    one page per array."""
+    one page per array.  base: rows of filler in front of the first page
+    (d_valid then covers them too).  A failed launch raises with .pages
+    added: the pages as they were left, None where .lens is negative."""
     rows = np.array([a.size for a in arrays], dtype=np.int32)
-    row_off = np.concatenate([[0], np.cumsum(rows)[:-1]]).astype(np.int64)
+    row_off = base + np.concatenate([[0], np.cumsum(rows)[:-1]]).astype(
+        np.int64)
     col = np.concatenate(arrays) if len(arrays) else np.zeros(0)
+    if base:
+        col = np.concatenate([np.full(base, 77, dtype=col.dtype), col])
     if col.size == 0:
         col = np.zeros(1, dtype=arrays[0].dtype)
     d_vals = torch.from_numpy(np.ascontiguousarray(col)).cuda()
@@ -310,8 +315,12 @@ def _encode(engine, kind, arrays, d_valid=None, cap=None):
         cap = int(rows.max()) * 12 + 128
     d_out = torch.zeros(len(arrays) * max(cap, 256), dtype=torch.uint8,
                         device="cuda")
-    lens = engine.encode_pages_dev(kind, d_vals, row_off, rows, d_out, cap,
-                                   d_valid=d_valid)
+    try:
+        lens = engine.encode_pages_dev(kind, d_vals, row_off, rows, d_out,
+                                       cap, d_valid=d_valid)
+    except RuntimeError as e:
+        e.pages = _pages_out(d_out, cap, e.lens)
+        raise
     return _pages_out(d_out, cap, lens)
 
 
@@ -467,6 +476,68 @@ def test_encode_error_i64_null(engine):
     assert ei.value.status == GS_ERR_FORMAT
     assert "decode" not in str(ei.value)
     assert ei.value.lens[0] > 0 and ei.value.lens[1] < 0
+    assert ei.value.pages[0] == gs.page_of(vals[0], gs.CT_I64)
+    _small_page_ok(engine)
+
+
+# Pages around the 256-row step of the prepare kernel, in one launch whose
+# first page does not start at row 0.
+_STEP_ROWS = (1, 9, 255, 256, 257, 513)
+_STEP_BASE = 7
+
+
+def test_encode_i64_all_ones_validity_takes_dense_route(engine):
+    """kind 1 with a validity array of ones: the column goes through the
+    dense scratch column and comes out as the all-valid host pages."""
+    rng = np.random.default_rng(411)
+    arrays = [rng.integers(-2**40, 2**40, n).astype(np.int64)
+              for n in _STEP_ROWS]
+    valid = np.ones(_STEP_BASE + sum(_STEP_ROWS), dtype=np.uint8)
+    pages = _encode(engine, 1, arrays, base=_STEP_BASE,
+                    d_valid=torch.from_numpy(valid).cuda())
+    for a, pg in zip(arrays, pages):
+        assert pg == gs.page_of(a, gs.CT_I64), a.size
+
+
+def test_encode_f64_nulls_across_the_prepare_step(engine):
+    """kind 2 with about 30 % nulls; rows 255 and 256 (the last of one
+    256-row step and the first of the next) are null in the 257-row page
+    and valid in the 513-row page.  Null slots hold the Gorilla sentinel."""
+    rng = np.random.default_rng(412)
+    sentinel = np.array([_sentinel_bits()], dtype=np.uint64).view(
+        np.float64)[0]
+    arrays, valids = [], []
+    for n in _STEP_ROWS:
+        vals = np.round(np.cumsum(rng.normal(0, 1, n)), 3)
+        valid = rng.random(n) > 0.3
+        if n == 257:
+            valid[255:257] = False
+        if n == 513:
+            valid[255:257] = True
+        vals[~valid] = sentinel
+        arrays.append(vals)
+        valids.append(valid)
+    valid_col = np.concatenate([np.ones(_STEP_BASE, dtype=bool)] + valids)
+    assert 0.2 < 1 - valid_col.mean() < 0.4
+    pages = _encode(engine, 2, arrays, base=_STEP_BASE,
+                    d_valid=torch.from_numpy(valid_col.astype(np.uint8)).cuda())
+    for vals, valid, pg in zip(arrays, valids, pages):
+        assert pg == gs.page_of(vals, gs.CT_F64, valid), vals.size
+
+
+def test_encode_error_ts_null(engine):
+    """kind 0 with one null row: GS_ERR_FORMAT with the entry's own
+    message, that page's length negative, the other page complete."""
+    vals = [T0 + np.arange(40, dtype=np.int64) * 1000,
+            T0 + np.arange(300, dtype=np.int64) ** 2]
+    valid = np.ones(340, dtype=np.uint8)
+    valid[40 + 256] = 0
+    with pytest.raises(RuntimeError) as ei:
+        _encode(engine, 0, vals, d_valid=torch.from_numpy(valid).cuda())
+    assert ei.value.status == GS_ERR_FORMAT
+    assert "null row in a ts/i64 page" in str(ei.value)
+    assert ei.value.lens[0] > 0 and ei.value.lens[1] < 0
+    assert ei.value.pages[0] == gs.page_of(vals[0], gs.CT_TIME)
     _small_page_ok(engine)
 
 

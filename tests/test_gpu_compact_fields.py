@@ -1,7 +1,9 @@
 """gs_compact_merge_fields: compaction merge over every field column of a
 column group (BatchMergeBuilder::take_last_and_merge,
 reader/batch_builder.rs:132-155 — per column the newest non-null value
-wins) vs the oracle restatement and vs per-column gs_compact_merge.
+wins) vs the oracle restatement.  gs_compact_merge is the same kernel at
+ncols=1, so the per-column comparisons below show that a column's result
+does not depend on its neighbours; the oracle is what says it is right.
 
 The oracle merges one float64 column; it serves every column type by
 merging global source-row ids (exact in float64 at these sizes) and
@@ -228,8 +230,9 @@ def _check(m, streams, dtypes, nseries, all_valid=False, tag=""):
 
 
 def _per_column_merge(engine, m, c):
-    """What a caller has to do without the new entry: gs_compact_merge of
-    column c alone."""
+    """Column c merged alone through gs_compact_merge: the group kernel at
+    ncols=1.  Equality with the group result shows independence from the
+    other columns, not correctness; every caller also runs _check."""
     d_ots = torch.zeros(m.total, dtype=torch.int64, device="cuda")
     d_oval = torch.zeros(m.total, dtype=torch.float64, device="cuda")
     d_ovd = torch.zeros(m.total, dtype=torch.uint8, device="cuda")

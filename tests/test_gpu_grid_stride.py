@@ -793,9 +793,9 @@ def test_group_by_tag(engine, cap):
 
 @pytest.mark.parametrize("cap", CAPS)
 def test_compaction(engine, cap):
-    """k_cm_flags, k_cm_prefix, k_cm_scatter_fields, then k_cm_scatter
-    (gs_compact_merge of column 0): 11 series, 3 streams, columns with
-    nulls and one absent column.  k_cm_prefix has 3 x 11 = 33 items, which
+    """k_cm_flags, k_cm_prefix, k_cm_scatter_fields, then the same three
+    at ncols=1 (gs_compact_merge of column 0): 11 series, 3 streams,
+    columns with nulls and one absent column.  k_cm_prefix has 3 x 11 = 33 items, which
     the 3-block stride divides: 11 whole trips at cap 3, 33 at cap 1."""
     import test_gpu_compact_fields as cf
     nseries = 11
@@ -824,13 +824,15 @@ def test_compaction(engine, cap):
 
 @pytest.mark.parametrize("cap", CAPS)
 def test_encode_pages(engine, cap):
-    """k_encode_pages: 1573 pages of 1..40 rows for each of the three kinds
-    of gs_encode_pages_dev, byte-exact against the host encoders.  The only
-    kernel here takes a page per thread: 2 * 768 + 37 pages make its third
-    trip at cap 3, and a ragged seventh at cap 1."""
+    """gs_encode_pages_dev, the one-column case of the group encode: 1573
+    pages of 1..40 rows for each of its three kinds, byte-exact against the
+    host encoders.  k_enc_prepare takes a page per block; k_enc_group_pages
+    takes a page per thread in 64-thread blocks: 8 * 192 + 37 pages make a
+    ragged ninth trip at cap 3, and a ragged 25th at cap 1."""
     rng = np.random.default_rng(20251109)
     npages = 1573
-    _ragged(npages, 256)
+    _ragged(npages)
+    _ragged(npages, 64)
     rows = (1 + (np.arange(npages) * 7) % 40).astype(np.int32)
     row_off = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
     total = int(rows.sum())

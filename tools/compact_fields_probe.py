@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Times gs_compact_merge_fields against gs_compact_merge on the
+"""Times gs_compact_merge_fields against gs_compact_merge (since the fold of
+the one-column kernel: the same kernel entered at ncols=1) on the
 `bench.py --mode compact` shape (config #5: k=8 overlapping L0 streams per
 series, each a random 25% subset of a shared grid) at a reduced series
 count, and writes the figures as JSON.
@@ -9,7 +10,11 @@ Legs, interleaved per repeat so that drift hits all of them alike:
   b  gs_compact_merge_fields, ncols=1
   c  gs_compact_merge_fields, ncols=8, all-valid
   d  gs_compact_merge_fields, ncols=8, 10% nulls per column
-  e  eight gs_compact_merge calls on the data of c (today's multi-field path)
+  e  eight gs_compact_merge calls on the data of c (the per-column route)
+
+Before timing, the ncols=8 result is compared with the per-column calls
+(one kernel at ncols=8 and at ncols=1: a column does not depend on its
+neighbours) and, for the first series, with the oracle's merge_dedup.
 
 Each call is host-synchronous (it ends in a stream synchronize), so the
 device events around it bracket the whole call: scratch allocation, the
@@ -98,8 +103,10 @@ def main():
               lambda: [single(c) for c in range(ncols)][-1]),
     }
 
-    # the new entry must compute what the per-column loop computes
-    out_rows = fields(ncols, False)
+    # a column's result must not depend on its neighbours ...
+    out_rows, offs = eng.compact_merge_fields(
+        gsets, tss, [[(vals[f][c], None) for c in range(ncols)]
+                     for f in range(k)], d_ots, outs)
     match = True
     for c in range(ncols):
         assert single(c) == out_rows
@@ -109,6 +116,20 @@ def main():
     if not match:
         sys.exit("gs_compact_merge_fields differs from per-column "
                  "gs_compact_merge")
+    # ... and must be the oracle's merge (first series, every column)
+    from oracle import pyoracle as orc
+    n0 = [int(t.numel()) // nseries for t in tss]
+    hts = [t[:n].cpu().numpy() for t, n in zip(tss, n0)]
+    lo, hi = int(offs[0]), int(offs[1])
+    for c in range(ncols):
+        uts, uval, _ = orc.merge_dedup(
+            [(hts[f], vals[f][c][:n0[f]].cpu().numpy(), None)
+             for f in range(k)])
+        if not (np.array_equal(d_ots[lo:hi].cpu().numpy(), uts) and
+                np.array_equal(outs[c][0][lo:hi].cpu().numpy().view(np.int64),
+                               uval.view(np.int64))):
+            sys.exit(f"gs_compact_merge_fields differs from the oracle "
+                     f"merge in column {c}")
 
     ms = {name: [] for name in legs}
     for rep in range(args.warmup + args.repeats):
@@ -131,7 +152,8 @@ def main():
               "repeats": args.repeats,
               "device": torch.cuda.get_device_name(0),
               "timing": "device events around each host-synchronous call",
-              "outputs_match_per_column_merge": True, "legs": {}}
+              "outputs_match_per_column_merge": True,
+              "first_series_matches_oracle": True, "legs": {}}
     for name, (what, nc, _) in legs.items():
         med = statistics.median(ms[name])
         result["legs"][name] = {

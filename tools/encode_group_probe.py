@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Times gs_encode_group_pages_dev against the routes that existed before
-it, on the merged output of the compact_fields_probe shape (k=8
-overlapping L0 streams per series, each a random 25% subset of a shared
-grid), split into 1000-row blocks per series, and writes the figures as
-JSON.
+"""Times gs_encode_group_pages_dev against the per-column routes (since the
+fold of the one-column kernel, gs_encode_pages_dev is the same two kernels
+entered with one column), on the merged output of the compact_fields_probe
+shape (k=8 overlapping L0 streams per series, each a random 25% subset of a
+shared grid), split into 1000-row blocks per series, and writes the figures
+as JSON.
 
 Legs, interleaved per repeat so that drift hits all of them alike:
   a_new  ts + one all-valid f64: one gs_encode_group_pages_dev call
@@ -15,8 +16,10 @@ Legs, interleaved per repeat so that drift hits all of them alike:
 
 Every call is host-synchronous, so the device events around a leg bracket
 all of it, host work included.  b_old also reports its copy time (host
-clock around the synchronous copies).  Before timing, every page the new
-call emits is compared with the old routes' pages.
+clock around the synchronous copies).  Before timing, every page the group
+call emits is compared with the per-column routes' pages (the same kernels
+with other neighbours) and with the host encoder's page (page_of), which is
+what says that the bytes are right.
 
     python tools/encode_group_probe.py --out profiles/encode_group.json
 """
@@ -170,10 +173,20 @@ def main():
         return [h[p * cap:p * cap + int(lens[p])].tobytes()
                 for p in range(npages)]
 
+    def host(v, ct, vd=None):  # the host encoder's pages of a device column
+        hv = v[:out_rows].cpu().numpy()
+        hvd = None if vd is None else vd[:out_rows].cpu().numpy().astype(bool)
+        return [gs.page_of(hv[o:o + n], ct,
+                           None if hvd is None else hvd[o:o + n])
+                for o, n in zip(row_off, rows)]
+
     ia, (lt, lf) = a_new(), a_old()
     same = cut(new_ts, cap_int, ia[0]["len"]) == cut(old_ts, cap_int, lt)
     same &= cut(new_cols[0], cap_f64, ia[1]["len"]) == \
         cut(old_cols[0], cap_f64, lf)
+    right = cut(new_ts, cap_int, ia[0]["len"]) == host(d_ts, gs.CT_TIME)
+    right &= cut(new_cols[0], cap_f64, ia[1]["len"]) == \
+        host(d_allvalid, gs.CT_F64)
     ib, lb = b_new(), b_old()
     same &= cut(new_ts, cap_int, ib[0]["len"]) == cut(old_ts, cap_int, lb["ts"])
     for c, dt in enumerate(MIX):
@@ -183,6 +196,12 @@ def main():
         same &= got == exp
     if not same:
         sys.exit("gs_encode_group_pages_dev pages differ from the old routes")
+    for c, dt in enumerate(MIX):
+        if dt == "f64":
+            right &= cut(new_cols[c], cap_f64, ib[1 + c]["len"]) == \
+                host(merged[c][0], gs.CT_F64, merged[c][1])
+    if not right:
+        sys.exit("device pages differ from the host encoder's pages")
     null_cells = sum(int(i["null_count"].sum()) for i in ib[1:])
     copy_s.clear()
 
@@ -220,7 +239,8 @@ def main():
         "warmup": args.warmup, "repeats": args.repeats,
         "device": torch.cuda.get_device_name(0),
         "timing": "device events around each host-synchronous leg",
-        "pages_match_old_routes": True, "legs": {}}
+        "pages_match_old_routes": True, "pages_match_host_encoder": True,
+        "legs": {}}
     for name in legs:
         med = statistics.median(ms[name])
         nc = 2 if name[0] == "a" else 1 + ncols
