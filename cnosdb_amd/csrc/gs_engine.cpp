@@ -21,6 +21,7 @@
 #include "gs_internal.h"
 #include "gs_gorilla.h"
 #include "gs_tsm_enc.h"
+#include "gs_str_dec.h"
 
 /* hipError_t returns are checked with HIP_TRY on every path that can fail
  * user-visibly; cleanup paths (hipFree/hipEventDestroy in destructors) and
@@ -99,6 +100,8 @@ __device__ __forceinline__ bool dev_varint(const uint8_t *p, uint32_t len,
 /* error codes accumulated into d_err */
 #define DERR_FORMAT 1u
 #define DERR_SHORT 2u
+static_assert(STR_ERR_FORMAT == DERR_FORMAT && STR_ERR_SHORT == DERR_SHORT,
+              "k_str_decode raises str_page_decode's verdict as is");
 #define DERR_NONMONO 4u /* a CRC-valid but non-monotonic time
                            page would silently mis-select rows via the
                            binary-search span/tombstone kernels; fail
@@ -1471,89 +1474,8 @@ __global__ void k_agg_partial_rle(const DevGroup *__restrict__ sg, int nsg,
  * is pages in flight: one thread decompresses one page into its scratch
  * slab, then walks the payload against the validity bitset recording
  * (pos,len) per row; a device scan of the lengths builds the Arrow
- * offsets and a gather packs the bytes. */
-
-__device__ int64_t dev_snappy_decompress(const uint8_t *__restrict__ src,
-                                         uint32_t len,
-                                         uint8_t *__restrict__ dst) {
-    uint64_t ulen = 0;
-    uint32_t i = 0;
-    int sh = 0, ok = 0;
-    while (i < len && i < 10) {
-        uint8_t b = src[i++];
-        ulen |= uint64_t(b & 0x7f) << sh;
-        sh += 7;
-        if (!(b & 0x80)) { ok = 1; break; }
-    }
-    if (!ok) return -1;
-    const uint8_t *ip = src + i, *end = src + len;
-    uint8_t *op = dst, *op_end = dst + ulen;
-    while (ip < end) {
-        uint8_t tag = *ip++;
-        uint32_t l, off;
-        switch (tag & 3) {
-        case 0: {
-            l = tag >> 2;
-            if (l >= 60) {
-                int c = int(l) - 59;
-                if (ip + c > end) return -1;
-                l = 0;
-                for (int k = 0; k < c; k++) l |= uint32_t(ip[k]) << (8 * k);
-                ip += c;
-            }
-            l += 1;
-            if (ip + l > end || op + l > op_end) return -1;
-            { /* word-wide literal copy (disjoint buffers; bounds above
-                 guarantee the 8-B reads/writes stay inside [ip,ip+l) /
-                 [op,op+l)) */
-                uint32_t k = 0;
-                for (; k + 8 <= l; k += 8) {
-                    uint64_t w;
-                    __builtin_memcpy(&w, ip + k, 8);
-                    __builtin_memcpy(op + k, &w, 8);
-                }
-                for (; k < l; k++) op[k] = ip[k];
-            }
-            ip += l;
-            op += l;
-            continue;
-        }
-        case 1:
-            if (ip >= end) return -1;
-            l = ((tag >> 2) & 7) + 4;
-            off = (uint32_t(tag >> 5) << 8) | *ip++;
-            break;
-        case 2:
-            if (ip + 2 > end) return -1;
-            l = (tag >> 2) + 1;
-            off = uint32_t(ip[0]) | (uint32_t(ip[1]) << 8);
-            ip += 2;
-            break;
-        default:
-            if (ip + 4 > end) return -1;
-            l = (tag >> 2) + 1;
-            off = uint32_t(ip[0]) | (uint32_t(ip[1]) << 8) |
-                  (uint32_t(ip[2]) << 16) | (uint32_t(ip[3]) << 24);
-            ip += 4;
-            break;
-        }
-        if (off == 0 || uint64_t(op - dst) < off || op + l > op_end) return -1;
-        const uint8_t *cp = op - off; /* may overlap: strictly in order */
-        if (off >= 8) { /* no overlap within a word: copy 8 B at a time */
-            uint32_t k = 0;
-            for (; k + 8 <= l; k += 8) {
-                uint64_t w;
-                __builtin_memcpy(&w, cp + k, 8);
-                __builtin_memcpy(op + k, &w, 8);
-            }
-            for (; k < l; k++) op[k] = cp[k];
-        } else { /* short offset: byte-serial repeat semantics */
-            for (uint32_t k = 0; k < l; k++) op[k] = cp[k];
-        }
-        op += l;
-    }
-    return (op == op_end && ip == end) ? int64_t(ulen) : -1;
-}
+ * offsets and a gather packs the bytes.  The decompressor, the walk and
+ * the slab accounting are gs_str_dec.h (shared with the host). */
 
 __global__ void k_str_decode(const uint8_t *__restrict__ blob,
                              const DevPage *__restrict__ pages, int n,
@@ -1567,66 +1489,14 @@ __global__ void k_str_decode(const uint8_t *__restrict__ blob,
          p += gridDim.x * blockDim.x) {
         DevPage pg = pages[p];
         const uint8_t *s = blob + pg.data_off;
-        const uint8_t *bs = blob + pg.bitset_off;
         const int64_t base = pg.row_off;
-        uint8_t *dst = scratch + scr_off[p];
-        for (uint32_t r = 0; r < pg.nrows; r++) {
-            sz[base + r] = 0;
-            pos[base + r] = 0;
-            if (valid) valid[base + r] = 0;
-        }
-        if (pg.data_len == 0) continue; /* empty src -> all null,
-                                           string.rs:231-236 */
-        /* normalize: the payload lands in this page's scratch slab for
-           both encodings, so the walk and the gather read one source */
-        int64_t pn;
-        int be = 0;
-        if (pg.enc == GS_ENC_SNAPPY) {
-            if (pg.data_len < 2) { atomicOr(err, DERR_FORMAT); continue; }
-            pn = dev_snappy_decompress(s + 2, pg.data_len - 2, dst);
-            if (pn < 0) { atomicOr(err, DERR_FORMAT); continue; }
-        } else if (pg.enc == GS_ENC_NULL) { /* string.rs:169-183 */
-            pn = int64_t(pg.data_len) - 1;
-            for (int64_t k = 0; k < pn; k++) dst[k] = s[1 + k];
-            be = 1;
-        } else {
-            atomicOr(err, DERR_FORMAT);
-            continue;
-        }
-        uint64_t i = 0;
-        for (uint32_t r = 0; r < pg.nrows; r++) {
-            int v = pg.all_valid ? 1 : dev_bit(bs, r);
-            if (!v) continue;
-            if (i >= uint64_t(pn)) { /* payload exhausted with valid rows
-                                        remaining: the reference emits a
-                                        SHORTER array here (rows dropped,
-                                        str_snappy_decode_to_array); fail
-                                        loudly instead of silently
-                                        nulling */
-                atomicOr(err, DERR_SHORT);
-                break;
-            }
-            uint64_t slen = 0;
-            if (be) {
-                if (i + 8 > uint64_t(pn)) { atomicOr(err, DERR_FORMAT); break; }
-                for (int k = 0; k < 8; k++) slen = (slen << 8) | dst[i + k];
-                i += 8;
-            } else {
-                int sh = 0, ok = 0;
-                while (i < uint64_t(pn)) {
-                    uint8_t b = dst[i++];
-                    slen |= uint64_t(b & 0x7f) << sh;
-                    sh += 7;
-                    if (!(b & 0x80)) { ok = 1; break; }
-                }
-                if (!ok) { atomicOr(err, DERR_FORMAT); break; }
-            }
-            if (i + slen > uint64_t(pn)) { atomicOr(err, DERR_FORMAT); break; }
-            pos[base + r] = scr_off[p] + int64_t(i);
-            sz[base + r] = int64_t(slen);
-            if (valid) valid[base + r] = 1;
-            i += slen;
-        }
+        /* the slab at scr_off[p] holds str_slab_size bytes of this page,
+           as gs_groups_upload laid it out */
+        unsigned e = str_page_decode(
+            s, pg.data_len, pg.enc, blob + pg.bitset_off, pg.all_valid,
+            pg.nrows, scratch + scr_off[p], scr_off[p], sz + base,
+            pos + base, valid ? valid + base : nullptr);
+        if (e) atomicOr(err, e);
     }
 }
 
@@ -3119,7 +2989,7 @@ struct SlotPages {
        host[PC_STR]) + total; caps parsed from the block headers at
        upload (snappy preamble varint / uncompressed payload length) */
     std::vector<int64_t> str_scr;
-    int64_t str_total = 0;
+    uint64_t str_total = 0;
     int64_t *d_str_scr = nullptr;
     /* Gorilla chunk table (page-major over host[PC_GOR]; states filled by
        the k_gor_sync upload pre-pass) */
@@ -3426,24 +3296,12 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
                       hp.dp.ctype == GS_CT_U64;
         if (hp.dp.ctype == GS_CT_STR) {
             cls = PC_STR;
-            /* scratch cap: decoded payload length (snappy preamble
-               varint, string.rs:197) or the raw payload (Null enc) */
-            int64_t cap = 0;
-            if (hp.dp.data_len >= 3 && hp.dp.enc == GS_ENC_SNAPPY) {
-                uint64_t v = 0;
-                int sh = 0;
-                for (uint32_t i = 2; i < hp.dp.data_len && i < 12; i++) {
-                    uint8_t b = hp.data_src[i];
-                    v |= uint64_t(b & 0x7f) << sh;
-                    sh += 7;
-                    if (!(b & 0x80)) break;
-                }
-                cap = int64_t(v);
-            } else if (hp.dp.data_len >= 1 && hp.dp.enc == GS_ENC_NULL) {
-                cap = int64_t(hp.dp.data_len) - 1;
-            }
-            sp.str_scr.push_back(sp.str_total);
-            sp.str_total += (cap + 15) & ~int64_t(15);
+            /* scratch slab: decoded payload length (snappy preamble
+               varint, string.rs:197, capped by what the stream can
+               produce) or the raw payload (Null enc) */
+            sp.str_scr.push_back(int64_t(sp.str_total));
+            sp.str_total += str_slab_stride(
+                str_slab_size(hp.data_src, hp.dp.data_len, hp.dp.enc));
         } else if (hp.dp.all_valid && hp.dp.sub == 2 && int_ct && hp.dp.data_len > 2) {
             if (hp.dp.enc == GS_ENC_DELTATS) cls = PC_RLE_TS;
             else if (hp.dp.enc == GS_ENC_DELTA) cls = PC_RLE_I64;
@@ -4168,7 +4026,7 @@ GsStatus gs_decode_str(GsCtx *ctx, GsGroupSet *set, uint32_t col,
     int n = sp.n[PC_STR];
     if (!set->d_str_scratch || set->str_scratch_cap < size_t(sp.str_total)) {
         if (set->d_str_scratch) hipFree(set->d_str_scratch);
-        size_t cap = sp.str_total > 0 ? size_t(sp.str_total) : 16;
+        size_t cap = sp.str_total ? size_t(sp.str_total) : 16;
         if (hipMalloc(&set->d_str_scratch, cap) != hipSuccess)
             return fail(GS_ERR, "hipMalloc string scratch failed");
         set->str_scratch_cap = cap;

@@ -162,10 +162,12 @@ GsGroupSet *gs_raw_set(GsCtx *ctx, const int64_t *counts, int64_t nseries);
  * int64[rows+1], exclusive prefix of byte lengths; null rows
  * contribute 0) and d_bytes (device, capacity bytes_cap).  d_valid
  * (device, 1 B/row, may be NULL) gets the validity bytes.  On return
- * *total_bytes = d_offsets[rows].  Rows whose page payload ends early
- * decode as null (the reference's builder stops appending).  Handles
- * GS_ENC_SNAPPY and GS_ENC_NULL blocks; empty data region -> all rows
- * null.  Current limit: rows <= 134M per set for the device offset
+ * *total_bytes = d_offsets[rows].  A page whose payload ends while valid
+ * rows remain fails the call (the reference's builder stops appending and
+ * returns a shorter array; rows are never silently nulled), and so does
+ * any malformed block.  Strings behind the last valid row are ignored.
+ * Handles GS_ENC_SNAPPY and GS_ENC_NULL blocks; empty data region -> all
+ * rows null.  Current limit: rows <= 134M per set for the device offset
  * scan. */
 GsStatus gs_decode_str(GsCtx *ctx, GsGroupSet *set, uint32_t col,
                        int64_t *d_offsets, uint8_t *d_bytes,

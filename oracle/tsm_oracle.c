@@ -1188,14 +1188,14 @@ ORC_EXPORT int64_t orc_str_decode(const uint8_t *src, size_t len,
         if (i >= pn) break; /* reference stops silently at payload end */
         uint64_t slen;
         if (be_lens) {
-            if (i + 8 > pn) { rc = -1; break; }
+            if (pn - i < 8) { rc = -1; break; }
             slen = 0;
             for (int k = 0; k < 8; k++) slen = (slen << 8) | pl[i + k];
             i += 8;
         } else {
             slen = 0;
             int sh = 0, ok = 0;
-            while (i < pn) {
+            while (i < pn && sh < 70) { /* a u64 varint has <= 10 bytes */
                 uint8_t b = pl[i++];
                 slen |= (uint64_t)(b & 0x7f) << sh;
                 sh += 7;
@@ -1203,7 +1203,8 @@ ORC_EXPORT int64_t orc_str_decode(const uint8_t *src, size_t len,
             }
             if (!ok) { rc = -1; break; }
         }
-        if (i + slen > pn || w + slen > bytes_cap) { rc = -1; break; }
+        /* against what is left: i + slen wraps for lengths near 2^64 */
+        if (slen > pn - i || slen > bytes_cap - w) { rc = -1; break; }
         memcpy(bytes_out + w, pl + i, slen);
         lens_out[r] = (int64_t)slen;
         i += slen;
