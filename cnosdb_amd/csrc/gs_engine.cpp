@@ -22,6 +22,7 @@
 #include "gs_gorilla.h"
 #include "gs_tsm_enc.h"
 #include "gs_str_dec.h"
+#include "gs_str_enc.h"
 
 /* hipError_t returns are checked with HIP_TRY on every path that can fail
  * user-visibly; cleanup paths (hipFree/hipEventDestroy in destructors) and
@@ -1943,6 +1944,60 @@ k_cm_scatter_fields(CompactFieldsArgs a, int nsets, int nseries,
     }
 }
 
+/* ---- string columns in the merge (gs_compact_merge_group).  To
+ * k_cm_scatter_fields a string column is an 8-byte column whose cell is a
+ * reference to the winning row: 1 + (stream << 48 | row), 0 for a null
+ * cell (the value the scatter's leftovers step stores).  The references of
+ * stream f are the same for each of its string columns, so one array per
+ * stream is materialised and the scatter kernel is the one the fixed-width
+ * columns run, unchanged.  Lengths, the offsets scan and the byte gather
+ * then run over the output rows only, with plain stores. */
+#define CM_REF_ROW_MASK ((1ULL << 48) - 1)
+
+struct CmStrSrc {
+    const int64_t *off[GS_MAX_STREAMS];
+    const uint8_t *bytes[GS_MAX_STREAMS];
+};
+
+__global__ void k_cm_str_refs(uint64_t *__restrict__ ref, int64_t rows, int f) {
+    for (int64_t r = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; r < rows;
+         r += int64_t(gridDim.x) * blockDim.x)
+        ref[r] = ((uint64_t(f) << 48) | uint64_t(r)) + 1;
+}
+
+__global__ void k_cm_str_lens(CmStrSrc s, const uint64_t *__restrict__ ref,
+                              int64_t n, int64_t *__restrict__ len) {
+    for (int64_t r = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; r < n;
+         r += int64_t(gridDim.x) * blockDim.x) {
+        const uint64_t x = ref[r];
+        int64_t l = 0;
+        if (x) {
+            const int64_t *o = s.off[(x - 1) >> 48] + ((x - 1) & CM_REF_ROW_MASK);
+            l = o[1] - o[0];
+        }
+        len[r] = l;
+    }
+}
+
+/* k_str_gather's copy with a per-row source base; byte by byte, since
+ * neither side has any alignment */
+__global__ void k_cm_str_gather(CmStrSrc s, const uint64_t *__restrict__ ref,
+                                const int64_t *__restrict__ off, int64_t n,
+                                uint8_t *__restrict__ out) {
+    for (int64_t r = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; r < n;
+         r += int64_t(gridDim.x) * blockDim.x) {
+        const uint64_t x = ref[r];
+        if (!x) continue;
+        const int f = int((x - 1) >> 48);
+        const int64_t so = s.off[f][(x - 1) & CM_REF_ROW_MASK];
+        const int64_t n2 = off[r + 1] - off[r];
+        const uint8_t *src = s.bytes[f] + so;
+        uint8_t *d = out + off[r];
+#pragma clang loop vectorize(disable) interleave(disable)
+        for (int64_t k = 0; k < n2; k++) d[k] = src[k];
+    }
+}
+
 /* --------------------------------------------------- fused filtered scan
  * Fast path of gs_scan when every ts page is RLE (the TSBS shape), every
  * field page is all-valid Gorilla and no tombstones apply: the span of
@@ -2938,6 +2993,199 @@ __global__ void k_enc_group_pages(const EncGroupCol *__restrict__ cols,
                              (const int64_t *)src + ps.row_off, size_t(nn),
                              data, nullptr);
         info[w].len = enc_seal_page(pg, bl, ps.nrows, data, dl, crct, err);
+    }
+}
+
+/* ---- string page re-encode (gs_encode_str_pages_dev): the pages of one
+ * string column, Arrow varbinary in HBM, as host.str_page_of writes them.
+ * The block encoder is gs_str_enc.h, the source gs_encode_str runs.  Two
+ * launches, one wave per page in both: k_str_enc_measure sizes each page's
+ * payload and checks its offsets, the host lays out one payload slab per
+ * page, and k_str_enc_pages builds bitset and payload with the whole wave
+ * and then lets lane 0 run the snappy match search, which is sequential by
+ * definition, so parallelism is pages in flight (as in k_str_decode and
+ * k_enc_group_pages).  Bytes of null rows are never read. */
+
+struct StrEncMeasure {
+    int64_t payload; /* sum(len + varint_len(len)) over the non-null rows */
+    int32_t nn;      /* non-null rows */
+    int32_t bad;     /* an offset decreases inside the page */
+};
+
+#define STR_ENC_THREADS 64
+/* strings up to this long are copied by their own lane, longer ones by the
+ * whole wave, one string at a time */
+#define STR_ENC_LANE_COPY 32
+
+__global__ __launch_bounds__(STR_ENC_THREADS) void k_str_enc_measure(
+    const int64_t *__restrict__ off, const uint8_t *__restrict__ valid,
+    const EncPageSpec *__restrict__ pages, int npages,
+    StrEncMeasure *__restrict__ out) {
+    const int lane = threadIdx.x;
+    for (int p = blockIdx.x; p < npages; p += gridDim.x) {
+        const EncPageSpec ps = pages[p];
+        const int64_t *o = off + ps.row_off;
+        const uint8_t *vd = valid ? valid + ps.row_off : nullptr;
+        int64_t payload = 0;
+        int32_t nn = 0, bad = 0;
+        for (int32_t r = lane; r < ps.nrows; r += STR_ENC_THREADS) {
+            const int64_t len = o[r + 1] - o[r];
+            if (len < 0) { bad = 1; continue; }
+            if (!vd || vd[r] != 0) {
+                nn++;
+                payload += len + int64_t(tsm_varint_len(uint64_t(len)));
+            }
+        }
+        for (int s = 32; s > 0; s >>= 1) {
+            payload += __shfl_xor(payload, s);
+            nn += __shfl_xor(nn, s);
+            bad |= __shfl_xor(bad, s);
+        }
+        if (lane == 0) {
+            out[p].payload = payload;
+            out[p].nn = nn;
+            out[p].bad = bad;
+        }
+    }
+}
+
+/* a < b as unsigned bytes, a proper prefix smaller (Rust slice Ord) */
+__device__ __forceinline__ int str_enc_cmp(const uint8_t *a, int64_t na,
+                                           const uint8_t *b, int64_t nb) {
+    const int64_t n = na < nb ? na : nb;
+    for (int64_t i = 0; i < n; i++)
+        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+    return na < nb ? -1 : na > nb ? 1 : 0;
+}
+
+/* (value, row) under "smaller value, then smaller row" is a total order, so
+ * the minimum is the same row for any partition of the rows; likewise
+ * "larger value, then smaller row" for the maximum.  Rows are page-relative,
+ * -1 = none. */
+__device__ __forceinline__ int str_enc_row_cmp(const int64_t *o,
+                                               const uint8_t *bytes, int32_t a,
+                                               int32_t b) {
+    return str_enc_cmp(bytes + o[a], o[a + 1] - o[a], bytes + o[b],
+                       o[b + 1] - o[b]);
+}
+__device__ __forceinline__ void str_enc_min_merge(const int64_t *o,
+                                                  const uint8_t *bytes,
+                                                  int32_t &m, int32_t r) {
+    if (r < 0) return;
+    if (m < 0) { m = r; return; }
+    const int c = str_enc_row_cmp(o, bytes, r, m);
+    if (c < 0 || (c == 0 && r < m)) m = r;
+}
+__device__ __forceinline__ void str_enc_max_merge(const int64_t *o,
+                                                  const uint8_t *bytes,
+                                                  int32_t &m, int32_t r) {
+    if (r < 0) return;
+    if (m < 0) { m = r; return; }
+    const int c = str_enc_row_cmp(o, bytes, r, m);
+    if (c > 0 || (c == 0 && r < m)) m = r;
+}
+
+/* One wave per page.  Per 64-row step the __ballot of the validity bytes is
+ * 8 bytes of the LSB-first bitset (validity loaded by bytes, as in
+ * k_enc_prepare), and a wave prefix sum of len + varint_len(len) over the
+ * non-null rows gives every string its place in the page's payload slab.
+ * Lane 0 then compresses the slab fragment by fragment, straight into the
+ * page, through the LDS hash table the wave zeroes for it; the same LDS
+ * holds the CRC table afterwards. */
+__global__ __launch_bounds__(STR_ENC_THREADS) void k_str_enc_pages(
+    const int64_t *__restrict__ off, const uint8_t *__restrict__ bytes,
+    const uint8_t *__restrict__ valid, const EncPageSpec *__restrict__ pages,
+    int npages, const int64_t *__restrict__ slab_off,
+    uint8_t *__restrict__ slabs, uint8_t *__restrict__ out, int64_t cap,
+    GsPageInfo *__restrict__ info, unsigned *__restrict__ err) {
+    __shared__ uint16_t tab[STR_ENC_MAX_TABLE];
+    const int lane = threadIdx.x;
+    for (int p = blockIdx.x; p < npages; p += gridDim.x) {
+        const EncPageSpec ps = pages[p];
+        const int32_t n = ps.nrows;
+        const int32_t bl = (n + 7) / 8;
+        const int64_t *o = off + ps.row_off;
+        const uint8_t *vd = valid ? valid + ps.row_off : nullptr;
+        uint8_t *pg = out + int64_t(p) * cap;
+        uint8_t *bs = pg + 16;
+        uint8_t *data = bs + bl;
+        uint8_t *slab = slabs + slab_off[p];
+
+        int64_t carry = 0; /* payload bytes before this step */
+        int32_t nn = 0, mnr = -1, mxr = -1;
+        for (int32_t base = 0; base < n; base += STR_ENC_THREADS) {
+            const int32_t r = base + lane;
+            const bool v = r < n && (!vd || vd[r] != 0);
+            const uint64_t b = __ballot(v);
+            if (lane < 8) {
+                const int32_t bi = (base >> 3) + lane;
+                if (bi < bl) bs[bi] = uint8_t(b >> (8 * lane));
+            }
+            nn += __popcll(b);
+            int64_t src = 0, len = 0, sz = 0;
+            if (v) {
+                src = o[r];
+                len = o[r + 1] - src;
+                sz = len + int64_t(tsm_varint_len(uint64_t(len)));
+            }
+            int64_t incl = sz;
+            for (int s = 1; s < 64; s <<= 1) {
+                const int64_t u = __shfl_up(incl, s);
+                if (lane >= s) incl += u;
+            }
+            int64_t dst = carry + incl - len; /* the string's bytes */
+            if (v) {
+                tsm_varint_put(slab + dst - (sz - len), uint64_t(len));
+                if (len <= STR_ENC_LANE_COPY)
+                    str_enc_copy(slab + dst, bytes + src, size_t(len));
+                str_enc_min_merge(o, bytes, mnr, r);
+                str_enc_max_merge(o, bytes, mxr, r);
+            }
+            uint64_t big = __ballot(v && len > STR_ENC_LANE_COPY);
+            while (big) {
+                const int l = __builtin_ctzll(big);
+                big &= big - 1;
+                const int64_t bsrc = __shfl(src, l), blen = __shfl(len, l);
+                const int64_t bdst = __shfl(dst, l);
+                for (int64_t i = lane; i < blen; i += STR_ENC_THREADS)
+                    slab[bdst + i] = bytes[bsrc + i];
+            }
+            carry += __shfl(incl, 63);
+        }
+        for (int s = 32; s > 0; s >>= 1) {
+            str_enc_min_merge(o, bytes, mnr, __shfl_xor(mnr, s));
+            str_enc_max_merge(o, bytes, mxr, __shfl_xor(mxr, s));
+        }
+        const int64_t payload = carry;
+
+        /* the slab is written by all lanes and read by lane 0 */
+        __threadfence();
+        __syncthreads();
+        int64_t dl = 0;
+        if (payload > 0) {
+            if (lane == 0) dl = int64_t(str_enc_block_header(data, uint64_t(payload)));
+            for (int64_t fo = 0; fo < payload; fo += STR_ENC_FRAGMENT) {
+                const size_t frag = payload - fo < int64_t(STR_ENC_FRAGMENT)
+                                        ? size_t(payload - fo)
+                                        : size_t(STR_ENC_FRAGMENT);
+                const uint32_t tsz = str_enc_table_size(frag);
+                for (uint32_t i = lane; i < tsz; i += STR_ENC_THREADS) tab[i] = 0;
+                __syncthreads();
+                if (lane == 0)
+                    dl = str_enc_fragment(slab + fo, frag, data + dl, tab) - data;
+                __syncthreads();
+            }
+        }
+        /* the hash table's LDS now holds the CRC table */
+        uint32_t *crct = (uint32_t *)tab;
+        enc_crc_table(crct);
+        if (lane == 0) {
+            info[p].len = enc_seal_page(pg, uint32_t(bl), n, data, dl, crct, err);
+            info[p].null_count = int64_t(n) - nn;
+            info[p].min_bits = mnr < 0 ? ~0ULL : uint64_t(ps.row_off + mnr);
+            info[p].max_bits = mxr < 0 ? ~0ULL : uint64_t(ps.row_off + mxr);
+        }
+        __syncthreads(); /* tab is zeroed again by the next page */
     }
 }
 
@@ -4865,6 +5113,98 @@ GsStatus gs_encode_pages_dev(GsCtx *ctx, int32_t kind, const void *d_vals,
     return st;
 }
 
+/* String pages: measure, check and lay out on the host, encode. */
+GsStatus gs_encode_str_pages_dev(GsCtx *ctx, const int64_t *d_offsets,
+                                 const uint8_t *d_bytes,
+                                 const uint8_t *d_valid,
+                                 const int64_t *h_row_off,
+                                 const int32_t *h_rows, int32_t npages,
+                                 uint8_t *d_out, int64_t cap_per_page,
+                                 GsPageInfo *h_info) {
+    if (!ctx || !d_offsets || !d_bytes || !h_row_off || !h_rows || !d_out ||
+        !h_info)
+        return fail(GS_ERR, "gs_encode_str_pages_dev: NULL argument");
+    if (npages <= 0)
+        return fail(GS_ERR, "gs_encode_str_pages_dev: npages <= 0");
+    for (int32_t p = 0; p < npages; p++)
+        if (h_rows[p] < 0 || h_row_off[p] < 0)
+            return fail(GS_ERR, "gs_encode_str_pages_dev: negative page "
+                                "offset or row count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<void *> scratch;
+    auto release = [&]() { for (void *q : scratch) hipFree(q); };
+    auto dalloc = [&](size_t bytes) -> void * {
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) return nullptr;
+        scratch.push_back(q);
+        return q;
+    };
+    std::vector<EncPageSpec> specs(npages);
+    for (int32_t p = 0; p < npages; p++) {
+        specs[p].row_off = h_row_off[p];
+        specs[p].nrows = h_rows[p];
+        specs[p].pad = 0;
+    }
+    EncPageSpec *d_specs = (EncPageSpec *)dalloc(specs.size() * sizeof(EncPageSpec));
+    StrEncMeasure *d_meas =
+        (StrEncMeasure *)dalloc(size_t(npages) * sizeof(StrEncMeasure));
+    int64_t *d_slab_off = (int64_t *)dalloc(size_t(npages) * sizeof(int64_t));
+    GsPageInfo *d_info = (GsPageInfo *)dalloc(size_t(npages) * sizeof(GsPageInfo));
+    if (!d_specs || !d_meas || !d_slab_off || !d_info) {
+        release();
+        return fail(GS_ERR, "hipMalloc string encode tables failed");
+    }
+    hipMemcpyAsync(d_specs, specs.data(), specs.size() * sizeof(EncPageSpec),
+                   hipMemcpyHostToDevice, ctx->stream);
+    hipLaunchKernelGGL(k_str_enc_measure, dim3(grid_for(npages, 1)),
+                       dim3(STR_ENC_THREADS), 0, ctx->stream, d_offsets,
+                       d_valid, d_specs, npages, d_meas);
+    std::vector<StrEncMeasure> meas(npages);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
+        hipMemcpy(meas.data(), d_meas, meas.size() * sizeof(StrEncMeasure),
+                  hipMemcpyDeviceToHost) != hipSuccess) {
+        release();
+        return fail(GS_ERR, "string encode: measure pass failed");
+    }
+    std::vector<int64_t> slab_off(npages);
+    int64_t slab_total = 0;
+    for (int32_t p = 0; p < npages; p++) {
+        if (meas[p].bad) {
+            release();
+            return fail(GS_ERR_FORMAT, "gs_encode_str_pages_dev: offsets "
+                                       "decrease inside a page");
+        }
+        const int64_t need = 16 + (int64_t(h_rows[p]) + 7) / 8 +
+                             int64_t(str_enc_max_len(uint64_t(meas[p].payload)));
+        if (cap_per_page < need) {
+            release();
+            return fail(GS_ERR_CAP, "gs_encode_str_pages_dev: cap_per_page "
+                                    "below worst-case encoded size");
+        }
+        slab_off[p] = slab_total;
+        slab_total += meas[p].payload;
+    }
+    uint8_t *d_slabs = (uint8_t *)dalloc(size_t(slab_total));
+    if (!d_slabs) {
+        release();
+        return fail(GS_ERR, "hipMalloc string payload slabs failed");
+    }
+    hipMemcpyAsync(d_slab_off, slab_off.data(), slab_off.size() * sizeof(int64_t),
+                   hipMemcpyHostToDevice, ctx->stream);
+    hipLaunchKernelGGL(k_str_enc_pages, dim3(grid_for(npages, 1)),
+                       dim3(STR_ENC_THREADS), 0, ctx->stream, d_offsets, d_bytes,
+                       d_valid, d_specs, npages, d_slab_off, d_slabs, d_out,
+                       cap_per_page, d_info, ctx->d_err);
+    GsStatus st = GS_OK;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess)
+        st = fail(GS_ERR, "string encode kernel failed");
+    else if (hipMemcpy(h_info, d_info, size_t(npages) * sizeof(GsPageInfo),
+                       hipMemcpyDeviceToHost) != hipSuccess)
+        st = fail(GS_ERR, "string encode: page info readback failed");
+    release();
+    return st;
+}
+
 /* Host-side setup of the merge: everything that depends
  * on the timestamps only.  Allocates the per-stream flag/prefix scratch,
  * runs k_cm_flags + k_cm_prefix once, and turns the per-(stream, series)
@@ -4938,6 +5278,203 @@ GsStatus cm_plan_ranks(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
 }
 } // namespace
 
+namespace {
+/* The merge behind gs_compact_merge, gs_compact_merge_fields (nstr == 0)
+ * and gs_compact_merge_group: the timestamp rank work runs once for any mix
+ * of columns.  `who` names the entry in messages. */
+GsStatus cm_merge_group(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
+                        int32_t ncols, const int32_t *elem_size,
+                        const int64_t *const *d_ts, const void *const *d_val,
+                        const uint8_t *const *d_valid, int32_t nstr,
+                        const GsStrColumn *str_in, int64_t *d_out_ts,
+                        void *const *d_out_val, uint8_t *const *d_out_valid,
+                        GsStrColumnOut *str_out, int64_t *h_out_offsets,
+                        int64_t *out_rows, const char *who) {
+    auto bad = [&](GsStatus st, const char *msg) {
+        return fail(st, (std::string(who) + ": " + msg).c_str());
+    };
+    if (!ctx || !sets || !d_ts || !d_out_ts ||
+        (ncols > 0 && (!elem_size || !d_val || !d_out_val)) ||
+        (nstr > 0 && (!str_in || !str_out)))
+        return bad(GS_ERR, "NULL argument");
+    if (nsets < 1 || nsets > GS_MAX_STREAMS)
+        return bad(GS_ERR, "nsets outside 1..GS_MAX_STREAMS");
+    const int nc = ncols + nstr;
+    if (ncols < 0 || nstr < 0 || nc < 1 || nc > GS_MAX_MERGE_COLS)
+        return bad(GS_ERR, "ncols + nstr outside 1..GS_MAX_MERGE_COLS");
+    uint32_t wide = 0;
+    for (int c = 0; c < ncols; c++) {
+        if (elem_size[c] != 8 && elem_size[c] != 1)
+            return bad(GS_ERR, "elem_size must be 8 or 1");
+        if (!d_out_val[c]) return bad(GS_ERR, "NULL output column");
+        if (elem_size[c] == 8) wide |= 1u << c;
+    }
+    for (int c = 0; c < nstr; c++) {
+        if (!str_out[c].d_offsets || !str_out[c].d_bytes ||
+            str_out[c].bytes_cap < 0)
+            return bad(GS_ERR, "NULL string output column");
+        wide |= 1u << (ncols + c);
+    }
+    for (int f = 0; f < nsets; f++)
+        if (!sets[f] || !d_ts[f]) return bad(GS_ERR, "NULL stream");
+    for (int i = 0; i < nsets * nstr; i++)
+        if (str_in[i].d_offsets && !str_in[i].d_bytes)
+            return bad(GS_ERR, "string column without bytes");
+    int nseries = sets[0]->nsgroups;
+    for (int f = 0; f < nsets; f++)
+        if (sets[f]->nsgroups != nseries)
+            return fail(GS_ERR, "all streams must cover the same series list");
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    CmPlan pl;
+    pl.nseries = nseries;
+    GsStatus st = cm_plan_ranks(ctx, sets, nsets, d_ts, pl);
+    /* an unsorted stream is known once the flags kernel has run */
+    if (st == GS_OK) st = check_dev_err(ctx);
+    const int64_t nout = st == GS_OK ? pl.ooff[nseries] : 0;
+    if (st == GS_OK && nstr > 0 &&
+        nout > int64_t(SCAN_BLOCK) * SCAN_ITEMS * 131072)
+        st = bad(GS_ERR, "string merge row limit exceeded (268M)");
+    if (st != GS_OK) {
+        hipStreamSynchronize(ctx->stream);
+        pl.release();
+        return st;
+    }
+    auto dalloc = [&](size_t bytes) -> void * {
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) return nullptr;
+        pl.scratch.push_back(q);
+        return q;
+    };
+    auto oom = [&]() {
+        hipStreamSynchronize(ctx->stream);
+        pl.release();
+        return bad(GS_ERR, "hipMalloc merge scratch failed");
+    };
+
+    /* string columns: one reference array per stream, one reference
+       column of the output per string column */
+    uint64_t *d_ref[GS_MAX_STREAMS] = {};
+    std::vector<uint64_t *> d_refout(nstr, nullptr);
+    if (nstr > 0) {
+        for (int f = 0; f < nsets; f++) {
+            const int64_t rows = sets[f]->total_rows;
+            if (!(d_ref[f] = (uint64_t *)dalloc(size_t(rows) * 8))) return oom();
+            hipLaunchKernelGGL(k_cm_str_refs, dim3(grid_for(rows, 256)),
+                               dim3(256), 0, ctx->stream, d_ref[f], rows, f);
+        }
+        for (int c = 0; c < nstr; c++)
+            if (!(d_refout[c] = (uint64_t *)dalloc(size_t(nout) * 8)))
+                return oom();
+    }
+
+    /* device pointer table: val | valid | out_val | out_valid */
+    const size_t ncell = size_t(nsets) * nc;
+    std::vector<const void *> tab(2 * ncell + 2 * size_t(nc), nullptr);
+    for (int f = 0; f < nsets; f++) {
+        for (int c = 0; c < ncols; c++) {
+            tab[f * nc + c] = d_val[f * ncols + c];
+            tab[ncell + f * nc + c] = d_valid ? d_valid[f * ncols + c] : nullptr;
+        }
+        for (int c = 0; c < nstr; c++) {
+            const GsStrColumn &in = str_in[f * nstr + c];
+            tab[f * nc + ncols + c] = in.d_offsets ? d_ref[f] : nullptr;
+            tab[ncell + f * nc + ncols + c] = in.d_valid;
+        }
+    }
+    for (int c = 0; c < ncols; c++) {
+        tab[2 * ncell + c] = d_out_val[c];
+        tab[2 * ncell + nc + c] = d_out_valid ? d_out_valid[c] : nullptr;
+    }
+    for (int c = 0; c < nstr; c++) {
+        tab[2 * ncell + ncols + c] = d_refout[c];
+        tab[2 * ncell + nc + ncols + c] = str_out[c].d_valid;
+    }
+    const void **d_tab = (const void **)dalloc(tab.size() * sizeof(void *));
+    if (!d_tab) return oom();
+    hipError_t he = hipMemcpyAsync(d_tab, tab.data(),
+                                   tab.size() * sizeof(void *),
+                                   hipMemcpyHostToDevice, ctx->stream);
+    if (he == hipSuccess) {
+        CompactFieldsArgs fa;
+        fa.m = pl.a;
+        fa.val = d_tab;
+        fa.valid = (const uint8_t *const *)(d_tab + ncell);
+        fa.out_val = (void *const *)(d_tab + 2 * ncell);
+        fa.out_valid = (uint8_t *const *)(d_tab + 2 * ncell + nc);
+        fa.wide = wide;
+        fa.ncols = nc;
+        hipLaunchKernelGGL(k_cm_scatter_fields, dim3(pl.gx, nsets), dim3(256),
+                           0, ctx->stream, fa, nsets, nseries, d_out_ts);
+    }
+    hipError_t hs = hipStreamSynchronize(ctx->stream);
+    if (he != hipSuccess || hs != hipSuccess) pl.release();
+    HIP_TRY(he);
+    HIP_TRY(hs);
+
+    /* string columns: lengths, offsets scan, capacity check, gather */
+    st = GS_OK;
+    if (nstr > 0) {
+        const int n = int(nout);
+        const int nblocks = (n + SCAN_BLOCK * SCAN_ITEMS - 1) /
+                            (SCAN_BLOCK * SCAN_ITEMS);
+        int64_t *d_len = (int64_t *)dalloc(size_t(n) * 8);
+        int64_t *d_bsums = (int64_t *)dalloc((size_t(nblocks) + 1) * 8);
+        if (!d_len || !d_bsums) return oom();
+        std::vector<CmStrSrc> srcs(nstr);
+        for (int c = 0; c < nstr; c++) {
+            for (int f = 0; f < GS_MAX_STREAMS; f++) {
+                const bool in = f < nsets;
+                srcs[c].off[f] = in ? str_in[f * nstr + c].d_offsets : nullptr;
+                srcs[c].bytes[f] = in ? str_in[f * nstr + c].d_bytes : nullptr;
+            }
+            int64_t *off = str_out[c].d_offsets;
+            if (n == 0) {
+                hipMemsetAsync(off, 0, 8, ctx->stream);
+                continue;
+            }
+            hipLaunchKernelGGL(k_cm_str_lens, dim3(grid_for(n, 256)), dim3(256),
+                               0, ctx->stream, srcs[c], d_refout[c],
+                               int64_t(n), d_len);
+            hipLaunchKernelGGL(k_scan_partials, dim3(nblocks), dim3(SCAN_BLOCK),
+                               0, ctx->stream, d_len, n, off, d_bsums);
+            hipLaunchKernelGGL(k_scan_fixup, dim3(1), dim3(64), 0, ctx->stream,
+                               n, off, d_bsums, nblocks);
+            hipLaunchKernelGGL(k_scan_add, dim3(grid_for(n, 256)), dim3(256), 0,
+                               ctx->stream, n, off, d_bsums);
+        }
+        std::vector<int64_t> totals(nstr, 0);
+        for (int c = 0; c < nstr; c++)
+            hipMemcpyAsync(&totals[c], str_out[c].d_offsets + n, 8,
+                           hipMemcpyDeviceToHost, ctx->stream);
+        hs = hipStreamSynchronize(ctx->stream);
+        if (hs != hipSuccess) pl.release();
+        HIP_TRY(hs);
+        for (int c = 0; c < nstr; c++) {
+            str_out[c].total_bytes = totals[c];
+            if (totals[c] > str_out[c].bytes_cap)
+                st = bad(GS_ERR_CAP, "a string column's bytes_cap is below "
+                                     "its total_bytes");
+        }
+        if (st == GS_OK && n > 0) {
+            for (int c = 0; c < nstr; c++)
+                hipLaunchKernelGGL(k_cm_str_gather, dim3(grid_for(n, 256)),
+                                   dim3(256), 0, ctx->stream, srcs[c],
+                                   d_refout[c], str_out[c].d_offsets,
+                                   int64_t(n), str_out[c].d_bytes);
+            hs = hipStreamSynchronize(ctx->stream);
+            if (hs != hipSuccess) pl.release();
+            HIP_TRY(hs);
+        }
+    }
+    pl.release();
+    if (h_out_offsets)
+        memcpy(h_out_offsets, pl.ooff.data(), size_t(nseries + 1) * 8);
+    if (out_rows) *out_rows = nout;
+    return st;
+}
+} // namespace
+
 GsStatus gs_compact_merge_fields(GsCtx *ctx, GsGroupSet *const *sets,
                                  int32_t nsets, int32_t ncols,
                                  const int32_t *elem_size,
@@ -4950,82 +5487,30 @@ GsStatus gs_compact_merge_fields(GsCtx *ctx, GsGroupSet *const *sets,
     if (!ctx || !sets || !elem_size || !d_ts || !d_val || !d_out_ts ||
         !d_out_val)
         return fail(GS_ERR, "bad args to gs_compact_merge_fields");
-    if (nsets < 1 || nsets > GS_MAX_STREAMS)
-        return fail(GS_ERR, "gs_compact_merge_fields: nsets outside "
-                            "1..GS_MAX_STREAMS");
-    if (ncols < 1 || ncols > GS_MAX_MERGE_COLS)
+    if (ncols < 1)
         return fail(GS_ERR, "gs_compact_merge_fields: ncols outside "
                             "1..GS_MAX_MERGE_COLS");
-    uint32_t wide = 0;
-    for (int c = 0; c < ncols; c++) {
-        if (elem_size[c] != 8 && elem_size[c] != 1)
-            return fail(GS_ERR, "gs_compact_merge_fields: elem_size must be "
-                                "8 or 1");
-        if (!d_out_val[c])
-            return fail(GS_ERR, "gs_compact_merge_fields: NULL output column");
-        if (elem_size[c] == 8) wide |= 1u << c;
-    }
-    for (int f = 0; f < nsets; f++)
-        if (!sets[f] || !d_ts[f])
-            return fail(GS_ERR, "gs_compact_merge_fields: NULL stream");
-    int nseries = sets[0]->nsgroups;
-    for (int f = 0; f < nsets; f++)
-        if (sets[f]->nsgroups != nseries)
-            return fail(GS_ERR, "all streams must cover the same series list");
-    HIP_TRY(hipSetDevice(ctx->device));
+    return cm_merge_group(ctx, sets, nsets, ncols, elem_size, d_ts, d_val,
+                          d_valid, 0, nullptr, d_out_ts, d_out_val,
+                          d_out_valid, nullptr, h_out_offsets, out_rows,
+                          "gs_compact_merge_fields");
+}
 
-    CmPlan pl;
-    pl.nseries = nseries;
-    GsStatus st = cm_plan_ranks(ctx, sets, nsets, d_ts, pl);
-    /* an unsorted stream is known once the flags kernel has run */
-    if (st == GS_OK) st = check_dev_err(ctx);
-    if (st != GS_OK) {
-        hipStreamSynchronize(ctx->stream);
-        pl.release();
-        return st;
-    }
-
-    /* device pointer table: val | valid | out_val | out_valid */
-    const size_t ncell = size_t(nsets) * ncols;
-    std::vector<const void *> tab(2 * ncell + 2 * size_t(ncols), nullptr);
-    for (size_t i = 0; i < ncell; i++) {
-        tab[i] = d_val[i];
-        tab[ncell + i] = d_valid ? d_valid[i] : nullptr;
-    }
-    for (int c = 0; c < ncols; c++) {
-        tab[2 * ncell + c] = d_out_val[c];
-        tab[2 * ncell + ncols + c] = d_out_valid ? d_out_valid[c] : nullptr;
-    }
-    const void **d_tab;
-    if (hipMalloc(&d_tab, tab.size() * sizeof(void *)) != hipSuccess) {
-        hipStreamSynchronize(ctx->stream);
-        pl.release();
-        return fail(GS_ERR, "hipMalloc compact pointer table failed");
-    }
-    pl.scratch.push_back(d_tab);
-    hipError_t he = hipMemcpyAsync(d_tab, tab.data(),
-                                   tab.size() * sizeof(void *),
-                                   hipMemcpyHostToDevice, ctx->stream);
-    if (he == hipSuccess) {
-        CompactFieldsArgs fa;
-        fa.m = pl.a;
-        fa.val = d_tab;
-        fa.valid = (const uint8_t *const *)(d_tab + ncell);
-        fa.out_val = (void *const *)(d_tab + 2 * ncell);
-        fa.out_valid = (uint8_t *const *)(d_tab + 2 * ncell + ncols);
-        fa.wide = wide;
-        fa.ncols = ncols;
-        hipLaunchKernelGGL(k_cm_scatter_fields, dim3(pl.gx, nsets), dim3(256),
-                           0, ctx->stream, fa, nsets, nseries, d_out_ts);
-    }
-    hipError_t hs = hipStreamSynchronize(ctx->stream);
-    pl.release();
-    HIP_TRY(he);
-    HIP_TRY(hs);
-    if (h_out_offsets)
-        memcpy(h_out_offsets, pl.ooff.data(), size_t(nseries + 1) * 8);
-    if (out_rows) *out_rows = pl.ooff[nseries];
-    return GS_OK;
+GsStatus gs_compact_merge_group(GsCtx *ctx, GsGroupSet *const *sets,
+                                int32_t nsets, int32_t ncols,
+                                const int32_t *elem_size,
+                                const int64_t *const *d_ts,
+                                const void *const *d_val,
+                                const uint8_t *const *d_valid, int32_t nstr,
+                                const GsStrColumn *str_in, int64_t *d_out_ts,
+                                void *const *d_out_val,
+                                uint8_t *const *d_out_valid,
+                                GsStrColumnOut *str_out,
+                                int64_t *h_out_offsets, int64_t *out_rows) {
+    return cm_merge_group(ctx, sets, nsets, ncols, elem_size, d_ts, d_val,
+                          d_valid, nstr, str_in, d_out_ts, d_out_val,
+                          d_out_valid, str_out, h_out_offsets, out_rows,
+                          "gs_compact_merge_group");
 }
 
 /* the one-column case of gs_compact_merge_fields: the per-stream d_val and

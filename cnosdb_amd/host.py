@@ -99,6 +99,17 @@ class GsScanResult(ctypes.Structure):
     ]
 
 
+class GsStrColumn(ctypes.Structure):
+    _fields_ = [("d_offsets", ctypes.c_void_p), ("d_bytes", ctypes.c_void_p),
+                ("d_valid", ctypes.c_void_p)]
+
+
+class GsStrColumnOut(ctypes.Structure):
+    _fields_ = [("d_offsets", ctypes.c_void_p), ("d_bytes", ctypes.c_void_p),
+                ("bytes_cap", ctypes.c_int64), ("d_valid", ctypes.c_void_p),
+                ("total_bytes", ctypes.c_int64)]
+
+
 # GsPageInfo as numpy sees it; min/max are re-viewed per column type
 _PAGE_INFO_DT = np.dtype([("len", "<i8"), ("null_count", "<i8"),
                           ("min", "<u8"), ("max", "<u8")])
@@ -189,6 +200,11 @@ class PageLib:
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
             ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p]
+        lib.gs_encode_str_pages_dev.restype = ctypes.c_int32
+        lib.gs_encode_str_pages_dev.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+            ctypes.c_int64, ctypes.c_void_p]
         lib.gs_export_group_column.restype = ctypes.c_int32
         lib.gs_export_group_column.argtypes = [
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -207,6 +223,16 @@ class PageLib:
             ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p,
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
             ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+        lib.gs_compact_merge_group.restype = ctypes.c_int32
+        lib.gs_compact_merge_group.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+            ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+            ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+            ctypes.POINTER(GsStrColumn), ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+            ctypes.POINTER(GsStrColumnOut), ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_int64)]
         lib.gs_debug_set_grid_cap.restype = ctypes.c_int32
         lib.gs_debug_set_grid_cap.argtypes = [ctypes.c_int32]
         lib.gs_debug_grid_rounds.restype = ctypes.c_int32
@@ -610,6 +636,66 @@ class Engine:
                 f"gs_compact_merge_fields failed ({st}): {self._pl.err()}")
         return rows.value, offs
 
+    def compact_merge_group(self, gsets, d_ts_list, cols, str_cols, d_out_ts,
+                            d_out_cols, str_outs):
+        """compact_merge_fields plus string columns
+        (gs_compact_merge_group).  cols / d_out_cols as in
+        compact_merge_fields (both may be empty lists per stream / empty);
+        str_cols[f][c] = (d_offsets, d_bytes, d_valid_or_None), decode_str's
+        layout, or None where column c is absent from stream f;
+        str_outs[c] = (d_offsets, d_bytes, d_valid_or_None).  Returns
+        (out_rows, per-series offsets np.array, [total_bytes per string
+        column]).  The exception of a failed call carries .status (GsStatus)
+        and .total_bytes (filled when the status is GS_ERR_CAP)."""
+        k = len(gsets)
+        ncols, nstr = len(d_out_cols), len(str_outs)
+        for f in range(k):
+            if len(cols[f]) != ncols or len(str_cols[f]) != nstr:
+                raise ValueError(f"stream {f}: column counts differ from "
+                                 "the outputs'")
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        sets = (ctypes.c_void_p * k)(*[g._h for g in gsets])
+        ts_p = (ctypes.c_void_p * k)(*[t.data_ptr() for t in d_ts_list])
+        ncell = max(k * ncols, 1)
+        val_p = (ctypes.c_void_p * ncell)(
+            *[ptr(cols[f][c][0]) for f in range(k) for c in range(ncols)])
+        vd_p = (ctypes.c_void_p * ncell)(
+            *[ptr(cols[f][c][1]) for f in range(k) for c in range(ncols)])
+        esz = (ctypes.c_int32 * max(ncols, 1))(
+            *[v.element_size() for v, _ in d_out_cols])
+        oval_p = (ctypes.c_void_p * max(ncols, 1))(
+            *[v.data_ptr() for v, _ in d_out_cols])
+        ovd_p = (ctypes.c_void_p * max(ncols, 1))(
+            *[ptr(v) for _, v in d_out_cols])
+        sin = (GsStrColumn * max(k * nstr, 1))()
+        for f in range(k):
+            for c in range(nstr):
+                col = str_cols[f][c]
+                if col is not None:
+                    sin[f * nstr + c] = GsStrColumn(
+                        col[0].data_ptr(), col[1].data_ptr(), ptr(col[2]))
+        sout = (GsStrColumnOut * max(nstr, 1))()
+        for c, (d_off, d_bytes, d_vd) in enumerate(str_outs):
+            sout[c] = GsStrColumnOut(d_off.data_ptr(), d_bytes.data_ptr(),
+                                     d_bytes.numel(), ptr(d_vd), -1)
+        nseries = self.lib.gs_set_series(gsets[0]._h)
+        offs = np.zeros(nseries + 1, dtype=np.int64)
+        rows = ctypes.c_int64(0)
+        st = self.lib.gs_compact_merge_group(
+            self._ctx, sets, k, ncols, esz, ts_p, val_p, vd_p, nstr, sin,
+            ctypes.c_void_p(d_out_ts.data_ptr()), oval_p, ovd_p, sout,
+            _np_ptr(offs), ctypes.byref(rows))
+        totals = [int(sout[c].total_bytes) for c in range(nstr)]
+        if st != 0:
+            e = RuntimeError(
+                f"gs_compact_merge_group failed ({st}): {self._pl.err()}")
+            e.status, e.total_bytes = st, totals
+            raise e
+        return rows.value, offs, totals
+
     def encode_pages_dev(self, kind, d_vals, row_off, rows, d_out,
                          cap_per_page, d_valid=None):
         """GPU page re-encode. kind: 0=ts 1=i64 2=f64. row_off/rows: host
@@ -673,6 +759,37 @@ class Engine:
             e.status, e.info = st, info
             raise e
         return info
+
+    def encode_str_pages_dev(self, d_offsets, d_bytes, row_off, rows, d_out,
+                             cap_per_page, d_valid=None):
+        """GPU re-encode of a string column's pages
+        (gs_encode_str_pages_dev).  d_offsets (int64, rows+1) and d_bytes
+        (uint8): the column in Arrow varbinary layout, as decode_str leaves
+        it; d_valid: uint8 per row or None.  Page p is written at
+        d_out[p*cap_per_page:] and equals str_page_of byte for byte.
+        Returns a structured array with fields len, null_count, min, max
+        ([npages]); min/max are the absolute ROW INDEX of the page's
+        smallest / largest value (bytewise order, smallest row among
+        equals), 2**64-1 for a page without a non-null value.  The
+        exception of a failed call carries .status (GsStatus)."""
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        npages = row_off.size
+        if rows.size != npages:
+            raise ValueError("row_off and rows differ in length")
+        info = np.zeros(max(npages, 1), dtype=_PAGE_INFO_DT)
+        st = self.lib.gs_encode_str_pages_dev(
+            self._ctx, ctypes.c_void_p(d_offsets.data_ptr()),
+            ctypes.c_void_p(d_bytes.data_ptr()),
+            ctypes.c_void_p(d_valid.data_ptr()) if d_valid is not None else None,
+            _np_ptr(row_off), _np_ptr(rows), npages,
+            ctypes.c_void_p(d_out.data_ptr()), cap_per_page, _np_ptr(info))
+        if st != 0:
+            e = RuntimeError(
+                f"gs_encode_str_pages_dev failed ({st}): {self._pl.err()}")
+            e.status = st
+            raise e
+        return info[:npages]
 
     def _mk_spec(self, d_ts, d_val, time_range, tombstones, d_out_ts,
                  d_out_val, agg, field_col=0):

@@ -383,6 +383,44 @@ GsStatus gs_encode_group_pages_dev(
     const int64_t *cap_per_page,   /* [ncols] */
     GsPageInfo *h_info);           /* [ncols*npages], index c*npages + p */
 
+/* ---- GPU re-encode of a string column's pages ----
+ * The DataType::Utf8 arm of Page::arrow_array_to_page (tsm/page.rs:299-325)
+ * on the device: the column in Arrow varbinary layout, as gs_decode_str
+ * leaves it (d_offsets int64[rows + 1], d_bytes, d_valid 1 B/row), cut into
+ * the pages h_row_off/h_rows.  Page p at d_out + p*cap_per_page is the page
+ * of the host path byte for byte: gs_encode_str over the non-null strings
+ * (codec/string.rs:32-88; the same source, csrc/gs_str_enc.h) under
+ * gs_build_page, with the LSB-first validity bitset.  A zero-row or
+ * all-null page has an empty data region.  Bytes of null rows are never
+ * read, whatever length the offsets give them.
+ *
+ * h_info[p].len and null_count are as in gs_encode_group_pages_dev.  The
+ * reference keeps a string page's min and max as byte strings
+ * (PageStatistics::Bytes, page.rs:313-324), which do not fit 64 bits, so
+ * min_bits / max_bits hold the ABSOLUTE ROW INDEX in the column of a row
+ * whose value is the page's minimum / maximum: unsigned bytewise
+ * lexicographic order, a proper prefix smaller (Rust slice Ord); among
+ * equal values the smallest row; UINT64_MAX in both for a page without a
+ * non-null value.
+ *
+ * A measure pass sizes every page's payload (sum of len + varint_len(len)
+ * over its non-null rows) before anything is written; the call holds one
+ * scratch buffer of that many bytes for its duration.
+ * Errors: GS_ERR (before any device work) for a NULL required pointer,
+ * npages <= 0 or a negative h_rows / h_row_off entry; GS_ERR_FORMAT when an
+ * offset decreases inside a page; GS_ERR_CAP when cap_per_page <
+ * 16 + ceil(rows/8) + 2 + 32 + payload + payload/6 for any page.  The last
+ * two are found by the measure pass: no byte of d_out is written.  A failed
+ * call leaves the context usable. */
+GsStatus gs_encode_str_pages_dev(
+    GsCtx *ctx,
+    const int64_t *d_offsets,  /* Arrow varbinary, as gs_decode_str leaves it */
+    const uint8_t *d_bytes,
+    const uint8_t *d_valid,    /* 1 B/row, NULL = all valid */
+    const int64_t *h_row_off, const int32_t *h_rows, int32_t npages,
+    uint8_t *d_out, int64_t cap_per_page,
+    GsPageInfo *h_info);       /* [npages] */
+
 /* ---- compaction merge (BASELINE config #5) ----
  * k overlapping L0 column-group streams per series -> one merged, deduped
  * (ts, value, validity) stream per series (tskv/src/compaction/compact.rs:
@@ -451,6 +489,55 @@ GsStatus gs_compact_merge_fields(
     int64_t *d_out_ts,
     void *const *d_out_val,                    /* [ncols] */
     uint8_t *const *d_out_valid,               /* [ncols]; entries or the array may be NULL */
+    int64_t *h_out_offsets, int64_t *out_rows);
+
+/* ---- compaction merge of a column group with string fields ----
+ * gs_compact_merge_fields plus nstr string columns (the DataType::Utf8
+ * fields of a column group, tsm/page.rs:299-325), each in Arrow varbinary
+ * layout as gs_decode_str leaves it.  A string column follows the rule of
+ * every other column (take_last_and_merge, batch_builder.rs:132-155): the
+ * newest stream that contains the timestamp, has the column and is valid
+ * there wins; with no such stream the cell is null with length 0.  A
+ * stream's column with d_offsets == NULL is absent there and behaves like
+ * an all-null column.  The merged column c is written as
+ * str_out[c].d_offsets (out_rows + 1 entries; the buffer holds the sum of
+ * input rows + 1), d_bytes and, when not NULL, d_valid; the result is what
+ * gs_encode_str_pages_dev takes.  Bytes of null input rows are never read.
+ *
+ * ncols >= 0, nstr >= 0 and 1 <= ncols + nstr <= GS_MAX_MERGE_COLS.  With
+ * nstr == 0 the call IS gs_compact_merge_fields (one internal function, so
+ * the timestamp rank work runs once for any mix of columns).  d_out_ts,
+ * the fixed-width outputs, h_out_offsets and out_rows are as there.
+ *
+ * GS_ERR as for gs_compact_merge_fields, and for more than 2^28 output
+ * rows with a string column (the device scan's limit).  GS_ERR_CAP when a
+ * column's total_bytes exceeds its bytes_cap: every str_out[c].total_bytes
+ * is filled, so the caller can size the buffers and call again, no d_bytes
+ * of any column is written, and everything else is as on success.  While
+ * it runs the call holds 8 B per input row (one reference array per
+ * stream) and 8 B per output row and string column. */
+typedef struct {                /* one stream's string column */
+    const int64_t *d_offsets;   /* int64[rows_f + 1]; NULL = column absent in this stream */
+    const uint8_t *d_bytes;
+    const uint8_t *d_valid;     /* NULL = all valid */
+} GsStrColumn;
+
+typedef struct {                /* one merged string column */
+    int64_t *d_offsets;         /* int64[sum of input rows + 1] */
+    uint8_t *d_bytes;
+    int64_t bytes_cap;
+    uint8_t *d_valid;           /* may be NULL */
+    int64_t total_bytes;        /* out: d_offsets[out_rows] */
+} GsStrColumnOut;
+
+GsStatus gs_compact_merge_group(
+    GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
+    int32_t ncols, const int32_t *elem_size,
+    const int64_t *const *d_ts, const void *const *d_val,
+    const uint8_t *const *d_valid,
+    int32_t nstr, const GsStrColumn *str_in,   /* [nsets*nstr], index f*nstr + c */
+    int64_t *d_out_ts, void *const *d_out_val, uint8_t *const *d_out_valid,
+    GsStrColumnOut *str_out,                   /* [nstr] */
     int64_t *h_out_offsets, int64_t *out_rows);
 
 /* ---- Arrow C Data Interface export (decode output as
