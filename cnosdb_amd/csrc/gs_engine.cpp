@@ -3,11 +3,8 @@
  * and the C-ABI host orchestration around them.
  *
  * Decode semantics mirror, bit-exactly:
- *   tskv/src/tsm/codec/timestamp.rs:177-299   (DeltaTs: sub-tag + scaler)
- *   tskv/src/tsm/codec/integer.rs:142-248     (Delta: zigzag)
- *   tskv/src/tsm/codec/simple8b.rs:80-208
+ *   timestamp / integer / simple8b / boolean pages: see gs_int_dec.h
  *   tskv/src/tsm/codec/float.rs:351-606       (Gorilla, sentinel-terminated)
- *   tskv/src/tsm/codec/boolean.rs:79-110
  *   tskv/src/tsm/reader.rs:494-560,634-656    (decode_pages + tombstone)
  *
  * MI355X mapping (this path is HBM-bandwidth-bound integer/bit work — no
@@ -22,6 +19,7 @@
 #include "gs_gorilla.h"
 #include "gs_tsm_enc.h"
 #include "gs_str_dec.h"
+#include "gs_int_dec.h"
 #include "gs_str_enc.h"
 
 /* hipError_t returns are checked with HIP_TRY on every path that can fail
@@ -74,9 +72,6 @@ __device__ __forceinline__ uint64_t dev_be64(const uint8_t *p) {
     __builtin_memcpy(&v, p, 8);
     return __builtin_bswap64(v);
 }
-__device__ __forceinline__ int64_t dev_zzdec(uint64_t v) {
-    return int64_t((v >> 1) ^ uint64_t(-int64_t(v & 1)));
-}
 __device__ __forceinline__ int dev_bit(const uint8_t *bs, uint32_t i) {
     return (bs[i >> 3] >> (i & 7)) & 1;
 }
@@ -85,76 +80,27 @@ __device__ __forceinline__ uint64_t dev_rotl64(uint64_t x, unsigned c) {
     return c ? (x << c) | (x >> (64 - c)) : x;
 }
 
-/* device varint (LEB128), integer_encoding crate semantics */
-__device__ __forceinline__ bool dev_varint(const uint8_t *p, uint32_t len,
-                                           uint64_t *out, uint32_t *nread) {
-    uint64_t v = 0;
-    int shift = 0;
-    for (uint32_t i = 0; i < len && i < 10; i++) {
-        v |= uint64_t(p[i] & 0x7f) << shift;
-        if (!(p[i] & 0x80)) { *out = v; *nread = i + 1; return true; }
-        shift += 7;
-    }
-    return false;
-}
-
 /* error codes accumulated into d_err */
 #define DERR_FORMAT 1u
 #define DERR_SHORT 2u
 static_assert(STR_ERR_FORMAT == DERR_FORMAT && STR_ERR_SHORT == DERR_SHORT,
               "k_str_decode raises str_page_decode's verdict as is");
+static_assert(INT_ERR_FORMAT == DERR_FORMAT && INT_ERR_SHORT == DERR_SHORT,
+              "the int and bool kernels raise gs_int_dec.h's verdicts as is");
 #define DERR_NONMONO 4u /* a CRC-valid but non-monotonic time
                            page would silently mis-select rows via the
                            binary-search span/tombstone kernels; fail
                            loudly instead (the reference's row-wise
                            filtering cannot mis-select) */
+static_assert(INT_ERR_NONMONO == DERR_NONMONO, "as above");
 /* raised by the encode kernels only, read by enc_dev_status */
 #define DERR_ENC_SENTINEL 8u /* Gorilla sentinel as an input value */
 #define DERR_ENC_NULL 16u    /* null row in a ts/i64 page */
 
-/* --------------------------------------------- pull-style value iterators */
-
-/* simple8b word stream (simple8b.rs:95-208), value extraction by index */
-struct DevS8b {
-    const uint8_t *p;
-    uint32_t len, pos;
-    uint64_t word;
-    int idx, cnt;
-    unsigned bits;
-    __device__ void init(const uint8_t *p_, uint32_t len_) {
-        p = p_; len = len_; pos = 0; idx = 0; cnt = 0; bits = 0; word = 0;
-    }
-    __device__ bool next(uint64_t *out) {
-        while (idx >= cnt) {
-            if (pos + 8 > len) return false;
-            word = dev_be64(p + pos);
-            pos += 8;
-            unsigned sel = unsigned(word >> 60);
-            const uint8_t COUNT[16] = {240, 120, 60, 30, 20, 15, 12, 10,
-                                       8, 7, 6, 5, 4, 3, 2, 1};
-            const uint8_t WIDTH[16] = {0, 0, 1, 2, 3, 4, 5, 6,
-                                       7, 8, 10, 12, 15, 20, 30, 60};
-            cnt = COUNT[sel];
-            bits = WIDTH[sel];
-            idx = 0;
-        }
-        if (bits == 0) { *out = 1; }
-        else {
-            uint64_t mask = (bits == 60) ? 0x0fffffffffffffffULL
-                                         : ((1ULL << bits) - 1);
-            *out = (word >> (unsigned(idx) * bits)) & mask;
-        }
-        idx++;
-        return true;
-    }
-};
-
-
 /* ---------------------------------------------------------------- kernels */
 
 /* Universal sequential decoder for int64-family pages (TIME/I64/U64):
- * one thread per page, grid-strided.  Handles DeltaTs/Delta with all three
- * sub-tags plus Null (raw BE), with validity-bitset scatter (null -> 0). */
+ * one thread per page, grid-strided (int_page_decode, gs_int_dec.h). */
 __global__ void k_seq_i64(const uint8_t *__restrict__ blob,
                           const DevPage *__restrict__ pages, int npages,
                           int64_t *__restrict__ out,
@@ -162,128 +108,12 @@ __global__ void k_seq_i64(const uint8_t *__restrict__ blob,
                           unsigned *__restrict__ err) {
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npages;
          p += gridDim.x * blockDim.x) {
-        DevPage pg = pages[p];
-        const uint8_t *data = blob + pg.data_off;
-        const uint8_t *bs = blob + pg.bitset_off;
-        int64_t *o = out + pg.row_off;
-        uint8_t *vd = valid ? valid + pg.row_off : nullptr;
-        uint32_t n = pg.nrows;
-
-        if (pg.data_len == 0) { /* all-null (timestamp.rs:181-185) */
-            for (uint32_t r = 0; r < n; r++) { o[r] = 0; if (vd) vd[r] = 0; }
-            continue;
-        }
-        uint8_t enc = pg.enc;
-        if (enc == GS_ENC_NULL) { /* raw BE per valid slot */
-            const uint8_t *q = data + 1;
-            uint32_t avail = (pg.data_len - 1) / 8, used = 0;
-            int64_t prev_ts = INT64_MIN;
-            for (uint32_t r = 0; r < n; r++) {
-                int v = pg.all_valid ? 1 : dev_bit(bs, r);
-                if (v && used < avail) {
-                    int64_t x = int64_t(dev_be64(q + 8ull * used)); used++;
-                    if (pg.ctype == GS_CT_TIME) {
-                        if (x < prev_ts) atomicOr(err, DERR_NONMONO);
-                        prev_ts = x;
-                    }
-                    o[r] = x;
-                }
-                else { o[r] = 0; v = 0; }
-                if (vd) vd[r] = uint8_t(v);
-            }
-            continue;
-        }
-        bool is_ts = (enc == GS_ENC_DELTATS);
-        if (!is_ts && enc != GS_ENC_DELTA) { atomicOr(err, DERR_FORMAT); continue; }
-        if (pg.data_len < 2) { atomicOr(err, DERR_FORMAT); continue; }
-        const uint8_t *s = data + 1;
-        uint32_t slen = pg.data_len - 1;
-        unsigned sub = s[0] >> 4;
-
-        if (sub == 0) { /* uncompressed deltas */
-            const uint8_t *q = s + 1;
-            uint32_t plen = slen - 1;
-            if (plen == 0 || (plen & 7)) { atomicOr(err, DERR_FORMAT); continue; }
-            uint32_t avail = plen / 8, used = 0;
-            int64_t prev = 0;
-            for (uint32_t r = 0; r < n; r++) {
-                int v = pg.all_valid ? 1 : dev_bit(bs, r);
-                if (!v) { o[r] = 0; if (vd) vd[r] = 0; continue; }
-                if (used >= avail) {
-                    if (!is_ts) { atomicOr(err, DERR_SHORT); }
-                    o[r] = 0; if (vd) vd[r] = uint8_t(is_ts ? 1 : 0);
-                    continue;
-                }
-                uint64_t raw = dev_be64(q + 8ull * used);
-                used++;
-                int64_t nxt = is_ts ? int64_t(uint64_t(prev) + raw)
-                                    : int64_t(uint64_t(prev) +
-                                              uint64_t(dev_zzdec(raw)));
-                if (is_ts && nxt < prev && used > 1)
-                    atomicOr(err, DERR_NONMONO);
-                prev = nxt;
-                o[r] = prev;
-                if (vd) vd[r] = 1;
-            }
-            continue;
-        }
-        if (sub == 2) { /* RLE */
-            uint64_t scaler = 1;
-            if (is_ts) {
-                unsigned s10 = s[0] & 0x0f;
-                for (unsigned k = 0; k < s10; k++) scaler *= 10;
-            }
-            const uint8_t *q = s + 1;
-            uint32_t plen = slen - 1;
-            if (plen < 9) { atomicOr(err, DERR_FORMAT); continue; }
-            uint64_t first_raw = dev_be64(q);
-            uint64_t dv; uint32_t nr;
-            if (!dev_varint(q + 8, plen - 8, &dv, &nr)) { atomicOr(err, DERR_FORMAT); continue; }
-            int64_t cur, delta;
-            if (is_ts) { cur = int64_t(first_raw); delta = int64_t(dv * scaler); }
-            else { cur = dev_zzdec(first_raw); delta = dev_zzdec(dv); }
-            if (is_ts && delta < 0 && n > 1) atomicOr(err, DERR_NONMONO);
-            bool first = true;
-            for (uint32_t r = 0; r < n; r++) {
-                int v = pg.all_valid ? 1 : dev_bit(bs, r);
-                if (!v) { o[r] = 0; if (vd) vd[r] = 0; continue; }
-                if (first) { o[r] = cur; first = false; }
-                else { cur = int64_t(uint64_t(cur) + uint64_t(delta)); o[r] = cur; }
-                if (vd) vd[r] = 1;
-            }
-            continue;
-        }
-        if (sub == 1) { /* simple8b */
-            uint64_t scaler = 1;
-            if (is_ts) {
-                unsigned s10 = s[0] & 0x0f;
-                for (unsigned k = 0; k < s10; k++) scaler *= 10;
-            }
-            const uint8_t *q = s + 1;
-            uint32_t plen = slen - 1;
-            if (plen < 8) { atomicOr(err, DERR_SHORT); continue; }
-            uint64_t first_raw = dev_be64(q);
-            int64_t cur = is_ts ? int64_t(first_raw) : dev_zzdec(first_raw);
-            DevS8b it;
-            it.init(q + 8, plen - 8);
-            bool first = true;
-            for (uint32_t r = 0; r < n; r++) {
-                int v = pg.all_valid ? 1 : dev_bit(bs, r);
-                if (!v) { o[r] = 0; if (vd) vd[r] = 0; continue; }
-                if (first) { o[r] = cur; first = false; if (vd) vd[r] = 1; continue; }
-                uint64_t u;
-                if (!it.next(&u)) { o[r] = 0; if (vd) vd[r] = 1; continue; } /* iterator exhaustion: builder skips */
-                int64_t nxt2 = is_ts ? int64_t(uint64_t(cur) + u * scaler)
-                                     : int64_t(uint64_t(cur) +
-                                               uint64_t(dev_zzdec(u)));
-                if (is_ts && nxt2 < cur) atomicOr(err, DERR_NONMONO);
-                cur = nxt2;
-                o[r] = cur;
-                if (vd) vd[r] = 1;
-            }
-            continue;
-        }
-        atomicOr(err, DERR_FORMAT);
+        const DevPage pg = pages[p];
+        const unsigned e = int_page_decode(
+            blob + pg.data_off, pg.data_len, pg.enc, pg.ctype == GS_CT_TIME,
+            blob + pg.bitset_off, pg.all_valid, pg.nrows, out + pg.row_off,
+            valid ? valid + pg.row_off : nullptr);
+        if (e) atomicOr(err, e);
     }
 }
 
@@ -713,7 +543,7 @@ __global__ void k_seq_f64(const uint8_t *__restrict__ blob,
     }
 }
 
-/* bool pages: one thread per page */
+/* bool pages: one thread per page (bool_page_decode, gs_int_dec.h) */
 __global__ void k_seq_bool(const uint8_t *__restrict__ blob,
                            const DevPage *__restrict__ pages, int npages,
                            uint8_t *__restrict__ out,
@@ -721,43 +551,12 @@ __global__ void k_seq_bool(const uint8_t *__restrict__ blob,
                            unsigned *__restrict__ err) {
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npages;
          p += gridDim.x * blockDim.x) {
-        DevPage pg = pages[p];
-        const uint8_t *data = blob + pg.data_off;
-        const uint8_t *bs = blob + pg.bitset_off;
-        uint8_t *o = out + pg.row_off;
-        uint8_t *vd = valid ? valid + pg.row_off : nullptr;
-        uint32_t n = pg.nrows;
-        if (pg.data_len == 0) {
-            for (uint32_t r = 0; r < n; r++) { o[r] = 0; if (vd) vd[r] = 0; }
-            continue;
-        }
-        if (pg.enc == GS_ENC_NULL) { /* boolean.rs:111-136 */
-            const uint8_t *q = data + 1;
-            uint32_t avail = pg.data_len - 1, used = 0;
-            for (uint32_t r = 0; r < n; r++) {
-                int v = pg.all_valid ? 1 : dev_bit(bs, r);
-                if (v && used < avail) { o[r] = (q[used] == 1); used++; }
-                else { o[r] = 0; v = 0; }
-                if (vd) vd[r] = uint8_t(v);
-            }
-            continue;
-        }
-        if (pg.enc != GS_ENC_BITPACK || pg.data_len < 2 ||
-            data[1] != (1 << 4)) { atomicOr(err, DERR_FORMAT); continue; }
-        uint64_t count; uint32_t nr;
-        if (!dev_varint(data + 2, pg.data_len - 2, &count, &nr)) {
-            atomicOr(err, DERR_FORMAT); continue;
-        }
-        const uint8_t *bits = data + 2 + nr;
-        uint64_t bi = 0;
-        for (uint32_t r = 0; r < n; r++) {
-            int v = pg.all_valid ? 1 : dev_bit(bs, r);
-            if (!v) { o[r] = 0; if (vd) vd[r] = 0; continue; }
-            if (bi >= count) { atomicOr(err, DERR_SHORT); o[r] = 0; if (vd) vd[r] = 0; continue; }
-            o[r] = (bits[bi >> 3] >> (7 - (bi & 7))) & 1;
-            bi++;
-            if (vd) vd[r] = 1;
-        }
+        const DevPage pg = pages[p];
+        const unsigned e = bool_page_decode(
+            blob + pg.data_off, pg.data_len, pg.enc, blob + pg.bitset_off,
+            pg.all_valid, pg.nrows, out + pg.row_off,
+            valid ? valid + pg.row_off : nullptr);
+        if (e) atomicOr(err, e);
     }
 }
 
@@ -767,31 +566,17 @@ __global__ void k_seq_bool(const uint8_t *__restrict__ blob,
 __global__ void k_rle_par(const uint8_t *__restrict__ blob,
                           const DevPage *__restrict__ pages, int npages,
                           int64_t *__restrict__ out,
-                          uint8_t *__restrict__ valid, int is_ts,
+                          uint8_t *__restrict__ valid,
                           unsigned *__restrict__ err) {
     for (int p = blockIdx.x; p < npages; p += gridDim.x) {
         DevPage pg = pages[p];
-        const uint8_t *s = blob + pg.data_off + 1;
-        uint32_t plen = pg.data_len - 2;
         /* every thread parses the tiny header redundantly (no sync needed) */
-        uint64_t scaler = 1;
-        if (is_ts) {
-            unsigned s10 = s[0] & 0x0f;
-            for (unsigned k = 0; k < s10; k++) scaler *= 10;
-        }
-        const uint8_t *q = s + 1;
-        if (plen < 9) { if (threadIdx.x == 0) atomicOr(err, DERR_FORMAT); continue; }
-        uint64_t first_raw = dev_be64(q);
-        uint64_t dv; uint32_t nr;
-        if (!dev_varint(q + 8, plen - 8, &dv, &nr)) {
-            if (threadIdx.x == 0) atomicOr(err, DERR_FORMAT);
-            continue;
-        }
-        int64_t first, delta;
-        if (is_ts) { first = int64_t(first_raw); delta = int64_t(dv * scaler); }
-        else { first = dev_zzdec(first_raw); delta = dev_zzdec(dv); }
-        if (is_ts && delta < 0 && pg.nrows > 1 && threadIdx.x == 0)
-            atomicOr(err, DERR_NONMONO);
+        const IntHeader h =
+            int_page_header(blob + pg.data_off, pg.data_len, pg.enc);
+        const unsigned e = h.verdict | int_rle_nonmono(h, pg.nrows);
+        if (e && threadIdx.x == 0) atomicOr(err, e);
+        if (h.verdict) continue;
+        const int64_t first = h.first, delta = h.rle_delta;
         int64_t *o = out + pg.row_off;
         uint8_t *vd = valid ? valid + pg.row_off : nullptr;
         for (uint32_t r = threadIdx.x; r < pg.nrows; r += blockDim.x) {
@@ -815,26 +600,19 @@ __global__ void k_s8b_par(const uint8_t *__restrict__ blob,
     __shared__ uint32_t scnt[256];
     __shared__ uint64_t ssum[256];
     __shared__ uint64_t carry[2]; /* [0]=value offset, [1]=delta prefix */
-    const uint8_t S8B_COUNT[16] = {240, 120, 60, 30, 20, 15, 12, 10,
-                                   8, 7, 6, 5, 4, 3, 2, 1};
-    const uint8_t S8B_WIDTH[16] = {0, 0, 1, 2, 3, 4, 5, 6,
-                                   7, 8, 10, 12, 15, 20, 30, 60};
     for (int p = blockIdx.x; p < npages; p += gridDim.x) {
         DevPage pg = pages[p];
-        const uint8_t *s = blob + pg.data_off + 1; /* sub-tag byte */
-        bool is_ts = pg.enc == GS_ENC_DELTATS;
-        uint64_t scaler = 1;
-        if (is_ts) {
-            unsigned s10 = s[0] & 0x0f;
-            for (unsigned k = 0; k < s10; k++) scaler *= 10;
+        const IntHeader h =
+            int_page_header(blob + pg.data_off, pg.data_len, pg.enc);
+        if (h.verdict) {
+            if (threadIdx.x == 0) atomicOr(err, h.verdict);
+            continue;
         }
-        const uint8_t *q = s + 1;
-        uint32_t plen = pg.data_len - 2;
-        if (plen < 8) { if (threadIdx.x == 0) atomicOr(err, DERR_SHORT); continue; }
-        uint64_t first_raw = dev_be64(q);
-        int64_t first = is_ts ? int64_t(first_raw) : dev_zzdec(first_raw);
-        const uint8_t *words = q + 8;
-        uint32_t nwords = (plen - 8) / 8;
+        const bool is_ts = h.is_ts;
+        const uint64_t scaler = h.scaler;
+        const int64_t first = h.first;
+        const uint8_t *words = h.payload;
+        uint32_t nwords = h.payload_len / 8;
         int64_t *o = out + pg.row_off;
         uint8_t *vd = valid ? valid + pg.row_off : nullptr;
         uint32_t n = pg.nrows;
@@ -851,26 +629,20 @@ __global__ void k_s8b_par(const uint8_t *__restrict__ blob,
             uint64_t w = 0;
             uint32_t cnt = 0;
             uint64_t dsum = 0;
-            unsigned sel = 0, bits = 0;
+            unsigned bits = 0;
             uint64_t mask = 0;
             if (wi < nwords) {
                 w = dev_be64(words + 8ull * wi);
-                sel = unsigned(w >> 60);
-                cnt = S8B_COUNT[sel];
-                bits = S8B_WIDTH[sel];
-                if (sel <= 1) {
+                int_s8b_word(w, cnt, bits, mask);
+                if (bits == 0) {
                     /* runs of "1": delta sum = cnt (x scaler for ts,
                        zigzag-decoded 1 -> -1 for i64) */
                     dsum = is_ts ? uint64_t(cnt) * scaler
                                  : uint64_t(int64_t(-1)) * cnt;
                 } else {
-                    mask = (bits == 60) ? 0x0fffffffffffffffULL
-                                        : ((1ULL << bits) - 1);
-                    uint64_t v = w;
                     for (uint32_t k = 0; k < cnt; k++) {
-                        uint64_t d = v & mask;
-                        dsum += is_ts ? d * scaler : uint64_t(dev_zzdec(d));
-                        v >>= bits;
+                        uint64_t d = int_s8b_get(w, k, bits, mask);
+                        dsum += is_ts ? d * scaler : uint64_t(int_zzdec(d));
                     }
                 }
             }
@@ -894,25 +666,23 @@ __global__ void k_s8b_par(const uint8_t *__restrict__ blob,
                             (threadIdx.x ? ssum[threadIdx.x - 1] : 0);
             if (wi < nwords && cnt) {
                 uint64_t acc = uint64_t(first) + dpre;
-                if (sel <= 1) {
+                if (bits == 0) {
                     uint64_t step = is_ts ? scaler : uint64_t(int64_t(-1));
                     for (uint32_t k = 0; k < cnt && voff + k < n; k++) {
                         acc += step;
                         o[voff + k] = int64_t(acc);
                     }
                 } else {
-                    uint64_t v = w;
                     int64_t pr = int64_t(acc);
                     for (uint32_t k = 0; k < cnt; k++) {
-                        uint64_t d = v & mask;
-                        acc += is_ts ? d * scaler : uint64_t(dev_zzdec(d));
+                        uint64_t d = int_s8b_get(w, k, bits, mask);
+                        acc += is_ts ? d * scaler : uint64_t(int_zzdec(d));
                         /* ts: i64 wrap of the delta prefix = corrupt page
                            (times must not decrease) */
                         if (is_ts && int64_t(acc) < pr)
                             atomicOr(err, DERR_NONMONO);
                         pr = int64_t(acc);
                         if (voff + k < n) o[voff + k] = int64_t(acc);
-                        v >>= bits;
                     }
                 }
             }
@@ -973,21 +743,19 @@ __global__ void k_bool_par(const uint8_t *__restrict__ blob,
                            unsigned *__restrict__ err) {
     for (int p = blockIdx.x; p < npages; p += gridDim.x) {
         DevPage pg = pages[p];
-        const uint8_t *data = blob + pg.data_off;
-        uint64_t count;
-        uint32_t nr;
-        if (pg.data_len < 3 || data[1] != (1 << 4) ||
-            !dev_varint(data + 2, pg.data_len - 2, &count, &nr)) {
-            if (threadIdx.x == 0) atomicOr(err, DERR_FORMAT);
+        const BoolHeader h =
+            bool_page_header(blob + pg.data_off, pg.data_len, pg.enc);
+        if (h.verdict) {
+            if (threadIdx.x == 0) atomicOr(err, h.verdict);
             continue;
         }
-        const uint8_t *bits = data + 2 + nr;
+        const uint64_t count = h.count; /* capped at the bits present */
         uint8_t *o = out + pg.row_off;
         uint8_t *vd = valid ? valid + pg.row_off : nullptr;
         uint32_t n = pg.nrows;
         if (count < n && threadIdx.x == 0) atomicOr(err, DERR_SHORT);
         for (uint32_t r = threadIdx.x; r < n; r += blockDim.x) {
-            o[r] = (r < count) ? ((bits[r >> 3] >> (7 - (r & 7))) & 1) : 0;
+            o[r] = (r < count) ? bool_bit(h.bits, r) : 0;
             if (vd) vd[r] = 1;
         }
     }
@@ -2101,18 +1869,15 @@ __global__ void k_spans_rle(const uint8_t *__restrict__ blob,
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npages;
          p += gridDim.x * blockDim.x) {
         DevPage pg = pages[p];
-        const uint8_t *s = blob + pg.data_off + 1;
-        uint64_t scaler = 1;
-        unsigned s10 = s[0] & 0x0f;
-        for (unsigned k = 0; k < s10; k++) scaler *= 10;
-        const uint8_t *q = s + 1;
-        int64_t first = int64_t(dev_be64(q));
-        uint64_t dv; uint32_t nr;
-        dev_varint(q + 8, pg.data_len - 10, &dv, &nr);
-        int64_t delta = int64_t(dv * scaler);
+        /* a page gs_decode refuses is refused here alike: empty span, and
+           the scan fails at its check of err */
+        const IntHeader h =
+            int_page_header(blob + pg.data_off, pg.data_len, pg.enc);
+        const int64_t first = h.first, delta = h.rle_delta;
         int64_t n = pg.nrows;
         int64_t st, en; /* selected rows = [st, en) */
-        if (delta < 0) { atomicOr(err, DERR_NONMONO); st = en = 0; }
+        if (h.verdict) { atomicOr(err, h.verdict); st = en = 0; }
+        else if (delta < 0) { atomicOr(err, DERR_NONMONO); st = en = 0; }
         else if (delta == 0) {
             bool in = first >= lo && first <= hi;
             st = 0; en = in ? n : 0;
@@ -3460,9 +3225,8 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
             hp.dp.nrows = ps.num_values;
             hp.dp.ctype = ps.ctype;
             hp.dp.enc = data_len ? data[0] : 0;
-            hp.dp.sub = (data_len >= 2 && (hp.dp.enc == GS_ENC_DELTA ||
-                                           hp.dp.enc == GS_ENC_DELTATS))
-                            ? (data[1] >> 4) : 0;
+            hp.dp.sub = uint8_t(
+                int_page_header(data, uint32_t(data_len), hp.dp.enc).sub);
             hp.dp.all_valid = av ? 1 : 0;
             hp.dp.grp = uint32_t(g);
             if (c == 0 && !av) {
@@ -3553,22 +3317,14 @@ GsGroupSet *gs_groups_upload(GsCtx *ctx, const GsColumnGroupDesc *groups,
         } else if (hp.dp.all_valid && hp.dp.sub == 2 && int_ct && hp.dp.data_len > 2) {
             if (hp.dp.enc == GS_ENC_DELTATS) cls = PC_RLE_TS;
             else if (hp.dp.enc == GS_ENC_DELTA) cls = PC_RLE_I64;
-            if (cls == PC_RLE_TS && hp.col == 0 && hp.dp.data_len > 10) {
-                /* RLE delta as k_spans_rle reads it: [enc][sub|log10
-                   scale][first BE64][varint delta]... */
-                uint64_t scaler = 1, dv = 0;
-                for (unsigned k = 0; k < (hp.data_src[1] & 0x0fu); k++)
-                    scaler *= 10;
-                int sh = 0;
-                for (uint32_t i = 10; i < hp.dp.data_len && sh < 64; i++) {
-                    uint8_t b = hp.data_src[i];
-                    dv |= uint64_t(b & 0x7f) << sh;
-                    sh += 7;
-                    if (!(b & 0x80)) break;
-                }
-                int64_t delta = int64_t(dv * scaler);
-                if (delta > 0 && delta < set->min_pos_delta)
-                    set->min_pos_delta = delta;
+            if (cls == PC_RLE_TS && hp.col == 0) {
+                /* RLE delta as k_spans_rle reads it; a page it refuses
+                   contributes nothing */
+                const IntHeader h = int_page_header(
+                    hp.data_src, hp.dp.data_len, hp.dp.enc);
+                if (!h.verdict && h.rle_delta > 0 &&
+                    h.rle_delta < set->min_pos_delta)
+                    set->min_pos_delta = h.rle_delta;
             }
         } else if (hp.dp.all_valid && hp.dp.sub == 1 && int_ct &&
                    (hp.dp.enc == GS_ENC_DELTATS || hp.dp.enc == GS_ENC_DELTA) &&
@@ -4149,13 +3905,13 @@ GsStatus gs_decode(GsCtx *ctx, GsGroupSet *set, uint32_t col, void *d_out,
                            dim3(grid_items(sp.n[PC_RLE_TS], 2048)),
                            dim3(256), 0, ctx->stream, set->d_blob,
                            sp.dev[PC_RLE_TS], sp.n[PC_RLE_TS], (int64_t *)d_out,
-                           d_valid, 1, ctx->d_err);
+                           d_valid, ctx->d_err);
     if (sp.n[PC_RLE_I64])
         hipLaunchKernelGGL(k_rle_par,
                            dim3(grid_items(sp.n[PC_RLE_I64], 2048)),
                            dim3(256), 0, ctx->stream, set->d_blob,
                            sp.dev[PC_RLE_I64], sp.n[PC_RLE_I64], (int64_t *)d_out,
-                           d_valid, 0, ctx->d_err);
+                           d_valid, ctx->d_err);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return check_dev_err(ctx);
 }

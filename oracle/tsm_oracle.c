@@ -702,6 +702,11 @@ ORC_EXPORT int orc_decode_bool(const uint8_t *src, size_t len, const uint8_t *bi
     uint64_t count; size_t nr;
     if (varint_get(s + 1, slen - 1, &count, &nr) != ORC_OK) return ORC_ERR_FORMAT;
     const uint8_t *bits = s + 1 + nr;
+    /* a count past the bits the block carries panics on the slice index in
+       the reference (boolean.rs:100); here the row that needs such a bit
+       is short */
+    const uint64_t have = 8 * (uint64_t)(slen - 1 - nr);
+    if (count > have) count = have;
     uint64_t bi = 0;
     for (int64_t r = 0; r < nrows; r++) {
         if (!bit_get(bitset, r)) { out[r] = 0; continue; }
