@@ -21,6 +21,7 @@
 #include "gs_str_dec.h"
 #include "gs_int_dec.h"
 #include "gs_str_enc.h"
+#include "gs_filter.h"
 
 /* hipError_t returns are checked with HIP_TRY on every path that can fail
  * user-visibly; cleanup paths (hipFree/hipEventDestroy in destructors) and
@@ -2954,6 +2955,171 @@ __global__ __launch_bounds__(STR_ENC_THREADS) void k_str_enc_pages(
     }
 }
 
+/* ------------------------------------------- column-group filter kernels
+ * gs_filter_group: DataFilter over a column group (reader/filter.rs:91-142)
+ * behind decode_pages' tombstones (tsm/reader.rs:494-560).  Every term of
+ * the keep rule is a function of one row, so the work item is a stretch of
+ * the set's ROW SPACE, not a group: every block does the same amount of work
+ * whatever the page size or the series count (k_rle_ts_tiles against
+ * k_rle_ts_filtered).  A wave owns FLT_SEG consecutive rows and walks them
+ * 64 at a time, a block of four waves a tile of FLT_TILE rows, and the
+ * kept count is kept PER WAVE SEGMENT: after the two-level scan over the
+ * segment counts each wave of the gather knows where its rows go, so
+ * neither kernel has LDS or a block barrier.  A kept row's rank inside the
+ * segment is popcount(ballot below the lane) plus the wave's running count
+ * of the steps before (the wave carry).  The cell rules are gs_filter.h's. */
+#define FLT_SEG 512                /* rows per wave: 8 steps of 64 */
+#define FLT_TILE (4 * FLT_SEG)     /* rows per 256-thread block */
+
+struct FltCol {              /* one column as the kernels see it */
+    const void *val;         /* 8 B/row, bool 1 B/row; unused for strings */
+    const uint8_t *valid;    /* NULL = all valid */
+    void *out_val;           /* gather; a string column's reference array */
+    uint8_t *out_valid;      /* gather; may be NULL */
+    int32_t rng_off;         /* this column's slice of the range table */
+    int32_t rng_cnt;
+    int32_t ctype;           /* GS_CT_* */
+    int32_t pad;
+};
+
+struct FltMaskArgs {
+    const int64_t *ts;
+    const GsTimeRange *ranges; /* normalised lists; the row tombstones first */
+    int64_t rows;
+    int64_t lo, hi;
+    int32_t row_rng_cnt;
+    int32_t npreds;
+    GsColPred pred[GS_MAX_FILTER_PREDS];
+    FltCol pcol[GS_MAX_FILTER_PREDS]; /* the column of pred[p] */
+};
+
+struct FltGatherArgs {
+    const int64_t *ts;
+    const GsTimeRange *ranges;
+    int64_t rows;
+    int32_t ncol;            /* projected columns only */
+    int32_t pad;
+    FltCol col[GS_MAX_MERGE_COLS];
+};
+
+__device__ __forceinline__ bool flt_effective(const FltCol &c,
+                                              const GsTimeRange *ranges,
+                                              int64_t r, int64_t t) {
+    if (c.valid && !c.valid[r]) return false; /* byte loads only */
+    return !(c.rng_cnt && flt_in_ranges(ranges + c.rng_off, c.rng_cnt, t));
+}
+
+/* mask[r] = the keep rule; seg_cnt[seg] = kept rows of the wave's segment */
+__global__ __launch_bounds__(256) void k_flt_mask(
+    FltMaskArgs a, int64_t nseg, uint8_t *__restrict__ mask,
+    int64_t *__restrict__ seg_cnt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t ntile = (nseg + 3) / 4;
+    for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+        const int64_t seg = tile * 4 + wave;
+        if (seg >= nseg) continue; /* wave-uniform; no barrier below */
+        int cnt = 0;
+        for (int s = 0; s < FLT_SEG / 64; s++) {
+            const int64_t r = seg * FLT_SEG + s * 64 + lane;
+            bool keep = false;
+            if (r < a.rows) {
+                const int64_t t = a.ts[r];
+                keep = t >= a.lo && t <= a.hi &&
+                       !(a.row_rng_cnt &&
+                         flt_in_ranges(a.ranges, a.row_rng_cnt, t));
+                for (int p = 0; p < a.npreds; p++) {
+                    if (!keep) break;
+                    const FltCol &c = a.pcol[p];
+                    const int op = a.pred[p].op;
+                    const bool ev = flt_effective(c, a.ranges, r, t);
+                    uint64_t x = 0;
+                    if (ev && !flt_op_is_null_test(op))
+                        x = c.ctype == GS_CT_BOOL
+                                ? uint64_t(((const uint8_t *)c.val)[r])
+                                : ((const uint64_t *)c.val)[r];
+                    keep = flt_cell(op, c.ctype, a.pred[p].a_bits,
+                                    a.pred[p].b_bits, x, ev);
+                }
+                mask[r] = keep;
+            }
+            cnt += __popcll(__ballot(keep));
+        }
+        if (lane == 0) seg_cnt[seg] = cnt;
+    }
+}
+
+/* kept rows to their output rows: timestamp, then value and validity of
+ * every projected column, 8-byte and 1-byte columns in the same launch, an
+ * effectively null cell as zero bytes.  A string column is an 8-byte column
+ * whose cell is the reference k_cm_str_lens / k_cm_str_gather take:
+ * 1 + row (stream 0), 0 for a null cell. */
+__global__ __launch_bounds__(256) void k_flt_gather(
+    FltGatherArgs a, int64_t nseg, const uint8_t *__restrict__ mask,
+    const int64_t *__restrict__ seg_off, int64_t *__restrict__ out_ts) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t ntile = (nseg + 3) / 4;
+    for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+        const int64_t seg = tile * 4 + wave;
+        if (seg >= nseg) continue;
+        int64_t base = seg_off[seg]; /* + the wave carry, step by step */
+        for (int s = 0; s < FLT_SEG / 64; s++) {
+            const int64_t r = seg * FLT_SEG + s * 64 + lane;
+            const bool m = r < a.rows && mask[r];
+            const uint64_t b = __ballot(m);
+            if (!b) continue;
+            if (m) {
+                const int64_t pos =
+                    base + __builtin_amdgcn_mbcnt_hi(
+                               uint32_t(b >> 32),
+                               __builtin_amdgcn_mbcnt_lo(uint32_t(b), 0u));
+                const int64_t t = a.ts[r];
+                out_ts[pos] = t;
+                for (int k = 0; k < a.ncol; k++) {
+                    const FltCol &c = a.col[k];
+                    const bool ev = flt_effective(c, a.ranges, r, t);
+                    if (c.out_valid) c.out_valid[pos] = ev;
+                    if (c.ctype == GS_CT_STR)
+                        ((uint64_t *)c.out_val)[pos] = ev ? uint64_t(r) + 1 : 0;
+                    else if (c.ctype == GS_CT_BOOL)
+                        ((uint8_t *)c.out_val)[pos] =
+                            ev ? ((const uint8_t *)c.val)[r] : uint8_t(0);
+                    else
+                        ((uint64_t *)c.out_val)[pos] =
+                            ev ? ((const uint64_t *)c.val)[r] : 0;
+                }
+            }
+            base += __popcll(b);
+        }
+    }
+}
+
+/* out_off[g] = output row at which group g's rows start (g == ng: the
+ * total): the prefix of the group's first row's segment plus the kept rows
+ * of that segment in front of the row.  One wave per group. */
+__global__ void k_flt_group_off(const DevGroup *__restrict__ groups, int ng,
+                                int64_t rows, const uint8_t *__restrict__ mask,
+                                const int64_t *__restrict__ seg_off,
+                                int64_t nseg, int64_t *__restrict__ out_off) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t(gridDim.x) * blockDim.x) >> 6;
+    for (int64_t g = (blockIdx.x * int64_t(blockDim.x) + threadIdx.x) >> 6;
+         g <= ng; g += nw) {
+        const int64_t r0 = g < ng ? groups[g].row_off : rows;
+        int64_t v;
+        if (r0 >= rows) {
+            v = seg_off[nseg];
+        } else {
+            const int64_t seg = r0 / FLT_SEG;
+            int c = 0;
+            for (int64_t r = seg * FLT_SEG + lane; r < r0; r += 64)
+                c += mask[r];
+            for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+            v = seg_off[seg] + c;
+        }
+        if (lane == 0) out_off[g] = v;
+    }
+}
+
 /* ------------------------------------------------------------- host state */
 
 struct GsCtx {
@@ -3080,6 +3246,14 @@ struct GsGroupSet {
     size_t ranges_cap = 0;
     uint8_t *d_valid = nullptr; /* lazily allocated internal validity bytes */
     uint8_t *d_mask = nullptr;  /* value-predicate row mask (lazy) */
+    /* gs_filter_group scratch (lazy, cached across calls): per-segment kept
+       counts, their prefix and the scan's block sums in one block; the
+       normalised range lists; the string reference columns and lengths */
+    int64_t *d_flt_seg = nullptr;
+    GsTimeRange *d_flt_ranges = nullptr;
+    size_t flt_ranges_cap = 0;
+    uint64_t *d_flt_ref = nullptr;
+    size_t flt_ref_cap = 0;
     int64_t *d_sel_cnt = nullptr; /* per-group masked selected counts (lazy) */
     bool any_nulls_field = false;
     /* agg partials: ngroups x nbuckets cells, cached across scans */
@@ -3603,6 +3777,9 @@ void gs_groups_free(GsGroupSet *set) {
     if (set->d_ranges) hipFree(set->d_ranges);
     if (set->d_valid) hipFree(set->d_valid);
     if (set->d_mask) hipFree(set->d_mask);
+    if (set->d_flt_seg) hipFree(set->d_flt_seg);
+    if (set->d_flt_ranges) hipFree(set->d_flt_ranges);
+    if (set->d_flt_ref) hipFree(set->d_flt_ref);
     if (set->d_sel_cnt) hipFree(set->d_sel_cnt);
     if (set->d_pmax) hipFree(set->d_pmax);
     if (set->d_psum) hipFree(set->d_psum);
@@ -5287,6 +5464,280 @@ GsStatus gs_compact_merge(GsCtx *ctx, GsGroupSet *const *sets, int32_t nsets,
                                    (const void *const *)d_val, d_valid,
                                    d_out_ts, &out_val, &out_valid,
                                    h_out_offsets, out_rows);
+}
+
+/* ---- DataFilter over a column group (see cnosdb_gs.h) ---- */
+
+/* debug: device time of the last gs_filter_group call, mask kernel to last
+   kernel, from HIP events on the engine stream (the probe's like-for-like
+   figure against GsScanResult.ms_filter + ms_compact) */
+static std::atomic<float> g_flt_ms{0.f};
+float gs_debug_filter_ms(void) {
+    return g_flt_ms.load(std::memory_order_relaxed);
+}
+/* debug: rows per block of the filter kernels, for the tests' edge sizes */
+int32_t gs_debug_filter_tile(void) { return FLT_TILE; }
+
+GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
+                         const GsFilterSpec *spec, int32_t ncols,
+                         const GsFilterCol *cols, int32_t nstr,
+                         const GsFilterStrCol *strs, int64_t *d_out_ts,
+                         int64_t *h_out_offsets, int64_t *out_rows) {
+    auto bad = [](const char *msg) {
+        return fail(GS_ERR, (std::string("gs_filter_group: ") + msg).c_str());
+    };
+    if (!ctx || !set || !d_ts || !spec || !d_out_ts || !h_out_offsets ||
+        !out_rows)
+        return bad("NULL argument");
+    if (ncols < 0 || nstr < 0 || ncols > GS_MAX_MERGE_COLS ||
+        nstr > GS_MAX_MERGE_COLS || ncols + nstr < 1 ||
+        ncols + nstr > GS_MAX_MERGE_COLS)
+        return bad("ncols + nstr outside 1..GS_MAX_MERGE_COLS");
+    const int npreds = spec->npreds;
+    if (npreds < 0 || npreds > GS_MAX_FILTER_PREDS)
+        return bad("npreds outside 0..GS_MAX_FILTER_PREDS");
+    if ((ncols > 0 && !cols) || (nstr > 0 && !strs) ||
+        (npreds > 0 && !spec->preds) ||
+        (spec->n_row_tombstones > 0 && !spec->row_tombstones))
+        return bad("NULL argument");
+    size_t nranges_in = spec->n_row_tombstones;
+    for (int c = 0; c < ncols; c++) {
+        const uint8_t ct = cols[c].ctype;
+        if (ct != GS_CT_I64 && ct != GS_CT_F64 && ct != GS_CT_BOOL &&
+            ct != GS_CT_U64)
+            return bad("column ctype must be i64, f64, bool or u64");
+        if (!cols[c].d_val || (cols[c].n_tombstones > 0 && !cols[c].tombstones))
+            return bad("NULL column pointer");
+        nranges_in += cols[c].n_tombstones;
+    }
+    for (int c = 0; c < nstr; c++) {
+        if (strs[c].n_tombstones > 0 && !strs[c].tombstones)
+            return bad("NULL column pointer");
+        const GsStrColumnOut *o = strs[c].out;
+        if (o && (!strs[c].in.d_offsets || !strs[c].in.d_bytes ||
+                  !o->d_offsets || !o->d_bytes || o->bytes_cap < 0))
+            return bad("NULL string column pointer");
+        nranges_in += strs[c].n_tombstones;
+    }
+    if (nranges_in > size_t(1) << 30) return bad("too many tombstone ranges");
+    for (int p = 0; p < npreds; p++) {
+        const GsColPred &pr = spec->preds[p];
+        if (!flt_op_known(pr.op)) return bad("unknown predicate op");
+        if (pr.col < 0 || pr.col >= ncols + nstr)
+            return bad("predicate column out of range");
+        if (pr.col >= ncols && !flt_op_is_null_test(pr.op))
+            return bad("a string column takes IS_NULL / IS_NOT_NULL only");
+    }
+    const int64_t rows = set->total_rows;
+    const int ng = int(set->ngroups);
+    if (nstr > 0 && rows > (int64_t(1) << 28))
+        return bad("string column row limit exceeded (2^28)");
+    const int64_t nseg = (rows + FLT_SEG - 1) / FLT_SEG;
+    if (nseg > INT32_MAX / 2) return bad("too many rows for the segment scan");
+
+    /* every range list in normal form, one table: row tombstones first */
+    std::vector<GsTimeRange> rtab;
+    rtab.reserve(nranges_in);
+    auto add_list = [&](const GsTimeRange *r, size_t n, int32_t &off,
+                        int32_t &cnt) {
+        off = int32_t(rtab.size());
+        rtab.insert(rtab.end(), r, r + n);
+        cnt = int32_t(flt_normalise(rtab.data() + off, int64_t(n)));
+        rtab.resize(size_t(off) + size_t(cnt));
+    };
+    int32_t row_off0 = 0, row_cnt = 0;
+    add_list(spec->row_tombstones, spec->n_row_tombstones, row_off0, row_cnt);
+    std::vector<FltCol> fc(size_t(ncols + nstr));
+    for (int c = 0; c < ncols; c++) {
+        FltCol &f = fc[c];
+        f.val = cols[c].d_val;
+        f.valid = cols[c].d_valid;
+        f.out_val = cols[c].d_out_val;
+        f.out_valid = cols[c].d_out_val ? cols[c].d_out_valid : nullptr;
+        f.ctype = cols[c].ctype;
+        f.pad = 0;
+        add_list(cols[c].tombstones, cols[c].n_tombstones, f.rng_off,
+                 f.rng_cnt);
+    }
+    std::vector<int> pstr; /* projected string columns */
+    for (int c = 0; c < nstr; c++) {
+        FltCol &f = fc[ncols + c];
+        f.val = nullptr;
+        f.valid = strs[c].in.d_valid;
+        f.out_val = nullptr; /* its reference array, below */
+        f.out_valid = strs[c].out ? strs[c].out->d_valid : nullptr;
+        f.ctype = GS_CT_STR;
+        f.pad = 0;
+        add_list(strs[c].tombstones, strs[c].n_tombstones, f.rng_off,
+                 f.rng_cnt);
+        if (strs[c].out) pstr.push_back(c);
+    }
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0) {
+        for (int c : pstr) {
+            HIP_TRY(hipMemsetAsync(strs[c].out->d_offsets, 0, 8, ctx->stream));
+            strs[c].out->total_bytes = 0;
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (int g = 0; g <= ng; g++) h_out_offsets[g] = 0;
+        *out_rows = 0;
+        return GS_OK;
+    }
+
+    /* scratch, cached in the set */
+    const int64_t scan_chunk = int64_t(SCAN_BLOCK) * SCAN_ITEMS;
+    const int64_t seg_blocks = (nseg + scan_chunk - 1) / scan_chunk;
+    if (!set->d_mask) HIP_TRY(hipMalloc(&set->d_mask, size_t(rows)));
+    if (!set->d_flt_seg)
+        HIP_TRY(hipMalloc(&set->d_flt_seg,
+                          size_t(2 * nseg + 1 + seg_blocks + 1) * 8));
+    int64_t *d_seg_cnt = set->d_flt_seg;
+    int64_t *d_seg_off = d_seg_cnt + nseg;        /* [nseg + 1] */
+    int64_t *d_seg_bsums = d_seg_off + nseg + 1;  /* [seg_blocks + 1] */
+    if (set->flt_ranges_cap < rtab.size()) {
+        if (set->d_flt_ranges) hipFree(set->d_flt_ranges);
+        set->d_flt_ranges = nullptr;
+        set->flt_ranges_cap = 0;
+        HIP_TRY(hipMalloc(&set->d_flt_ranges,
+                          rtab.size() * sizeof(GsTimeRange)));
+        set->flt_ranges_cap = rtab.size();
+    }
+    /* per projected string column a reference array, then the lengths and
+       the offset scan's block sums */
+    const int64_t row_blocks = (rows + scan_chunk - 1) / scan_chunk;
+    const size_t ref_need =
+        pstr.empty() ? 0
+                     : (pstr.size() + 1) * size_t(rows) + size_t(row_blocks) + 1;
+    if (set->flt_ref_cap < ref_need) {
+        if (set->d_flt_ref) hipFree(set->d_flt_ref);
+        set->d_flt_ref = nullptr;
+        set->flt_ref_cap = 0;
+        HIP_TRY(hipMalloc(&set->d_flt_ref, ref_need * 8));
+        set->flt_ref_cap = ref_need;
+    }
+    for (size_t k = 0; k < pstr.size(); k++)
+        fc[ncols + pstr[k]].out_val = set->d_flt_ref + k * size_t(rows);
+
+    hipEvent_t ev[2];
+    HIP_TRY(hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) {
+        hipEventDestroy(ev[0]);
+        return bad("hipEventCreate failed");
+    }
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard() { hipEventDestroy(e[0]); hipEventDestroy(e[1]); }
+    } guard{ev};
+
+    if (!rtab.empty())
+        HIP_TRY(hipMemcpyAsync(set->d_flt_ranges, rtab.data(),
+                               rtab.size() * sizeof(GsTimeRange),
+                               hipMemcpyHostToDevice, ctx->stream));
+    FltMaskArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.ts = d_ts;
+    ma.ranges = set->d_flt_ranges;
+    ma.rows = rows;
+    ma.lo = spec->range.min_ts;
+    ma.hi = spec->range.max_ts;
+    ma.row_rng_cnt = row_cnt;
+    ma.npreds = npreds;
+    for (int p = 0; p < npreds; p++) {
+        ma.pred[p] = spec->preds[p];
+        ma.pcol[p] = fc[spec->preds[p].col];
+    }
+    FltGatherArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.ts = d_ts;
+    ga.ranges = set->d_flt_ranges;
+    ga.rows = rows;
+    for (const FltCol &f : fc)
+        if (f.out_val) ga.col[ga.ncol++] = f;
+
+    const int64_t ntile = (nseg + 3) / 4;
+    HIP_TRY(hipEventRecord(ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_flt_mask, dim3(grid_items(ntile, 2048)), dim3(256), 0,
+                       ctx->stream, ma, nseg, set->d_mask, d_seg_cnt);
+    {
+        const int n = int(nseg);
+        const int nblocks = int(seg_blocks);
+        hipLaunchKernelGGL(k_scan_partials, dim3(nblocks), dim3(SCAN_BLOCK), 0,
+                           ctx->stream, d_seg_cnt, n, d_seg_off, d_seg_bsums);
+        hipLaunchKernelGGL(k_scan_fixup, dim3(1), dim3(64), 0, ctx->stream, n,
+                           d_seg_off, d_seg_bsums, nblocks);
+        hipLaunchKernelGGL(k_scan_add, dim3(grid_for(n, 256)), dim3(256), 0,
+                           ctx->stream, n, d_seg_off, d_seg_bsums);
+    }
+    hipLaunchKernelGGL(k_flt_gather, dim3(grid_items(ntile, 2048)), dim3(256),
+                       0, ctx->stream, ga, nseg, set->d_mask, d_seg_off,
+                       d_out_ts);
+    hipLaunchKernelGGL(k_flt_group_off,
+                       dim3(grid_for((int64_t(ng) + 1) * 64, 256)), dim3(256),
+                       0, ctx->stream, set->d_groups, ng, rows, set->d_mask,
+                       d_seg_off, nseg, set->d_out_off);
+    HIP_TRY(hipEventRecord(ev[1], ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_out_offsets, set->d_out_off,
+                           (size_t(ng) + 1) * 8, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const int64_t nout = h_out_offsets[ng];
+    *out_rows = nout;
+
+    /* string columns: lengths, offsets scan, capacity check, gather — the
+       kernels of gs_compact_merge_group over one stream */
+    GsStatus st = GS_OK;
+    if (!pstr.empty()) {
+        const int n = int(nout);
+        const int nblocks = int((nout + scan_chunk - 1) / scan_chunk);
+        int64_t *d_len = (int64_t *)(set->d_flt_ref + pstr.size() * size_t(rows));
+        int64_t *d_bsums = d_len + rows;
+        std::vector<CmStrSrc> srcs(pstr.size());
+        std::vector<int64_t> totals(pstr.size(), 0);
+        for (size_t k = 0; k < pstr.size(); k++) {
+            const GsFilterStrCol &sc = strs[pstr[k]];
+            memset(&srcs[k], 0, sizeof(CmStrSrc));
+            srcs[k].off[0] = sc.in.d_offsets;
+            srcs[k].bytes[0] = sc.in.d_bytes;
+            int64_t *off = sc.out->d_offsets;
+            const uint64_t *ref = set->d_flt_ref + k * size_t(rows);
+            if (n == 0) {
+                HIP_TRY(hipMemsetAsync(off, 0, 8, ctx->stream));
+                continue;
+            }
+            hipLaunchKernelGGL(k_cm_str_lens, dim3(grid_for(n, 256)), dim3(256),
+                               0, ctx->stream, srcs[k], ref, int64_t(n), d_len);
+            hipLaunchKernelGGL(k_scan_partials, dim3(nblocks), dim3(SCAN_BLOCK),
+                               0, ctx->stream, d_len, n, off, d_bsums);
+            hipLaunchKernelGGL(k_scan_fixup, dim3(1), dim3(64), 0, ctx->stream,
+                               n, off, d_bsums, nblocks);
+            hipLaunchKernelGGL(k_scan_add, dim3(grid_for(n, 256)), dim3(256), 0,
+                               ctx->stream, n, off, d_bsums);
+            HIP_TRY(hipMemcpyAsync(&totals[k], off + n, 8,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (size_t k = 0; k < pstr.size(); k++) {
+            GsStrColumnOut *o = strs[pstr[k]].out;
+            o->total_bytes = totals[k];
+            if (totals[k] > o->bytes_cap)
+                st = fail(GS_ERR_CAP, "gs_filter_group: a string column's "
+                                      "bytes_cap is below its total_bytes");
+        }
+        if (st == GS_OK && n > 0) {
+            for (size_t k = 0; k < pstr.size(); k++)
+                hipLaunchKernelGGL(k_cm_str_gather, dim3(grid_for(n, 256)),
+                                   dim3(256), 0, ctx->stream, srcs[k],
+                                   set->d_flt_ref + k * size_t(rows),
+                                   strs[pstr[k]].out->d_offsets, int64_t(n),
+                                   strs[pstr[k]].out->d_bytes);
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+        g_flt_ms.store(ms, std::memory_order_relaxed);
+    return st;
 }
 
 /* ---- Arrow C Data Interface export ---- */

@@ -110,6 +110,79 @@ class GsStrColumnOut(ctypes.Structure):
                 ("total_bytes", ctypes.c_int64)]
 
 
+class GsColPred(ctypes.Structure):
+    _fields_ = [("col", ctypes.c_int32), ("op", ctypes.c_int32),
+                ("a_bits", ctypes.c_uint64), ("b_bits", ctypes.c_uint64)]
+
+
+class GsFilterCol(ctypes.Structure):
+    _fields_ = [("ctype", ctypes.c_uint8), ("d_val", ctypes.c_void_p),
+                ("d_valid", ctypes.c_void_p),
+                ("tombstones", ctypes.POINTER(GsTimeRange)),
+                ("n_tombstones", ctypes.c_size_t),
+                ("d_out_val", ctypes.c_void_p),
+                ("d_out_valid", ctypes.c_void_p)]
+
+
+class GsFilterStrCol(ctypes.Structure):
+    _fields_ = [("in_", GsStrColumn),
+                ("tombstones", ctypes.POINTER(GsTimeRange)),
+                ("n_tombstones", ctypes.c_size_t),
+                ("out", ctypes.POINTER(GsStrColumnOut))]
+
+
+class GsFilterSpec(ctypes.Structure):
+    _fields_ = [("range", GsTimeRange),
+                ("row_tombstones", ctypes.POINTER(GsTimeRange)),
+                ("n_row_tombstones", ctypes.c_size_t),
+                ("preds", ctypes.POINTER(GsColPred)),
+                ("npreds", ctypes.c_int32)]
+
+
+# gs_filter_group's ops: gs_scan's seven plus the two null tests
+FILTER_OPS = dict(PRED_OPS, is_null=8, is_not_null=9)
+
+
+def pred_bits(ctype, value):
+    """A predicate constant as raw bits in the column's own type (GsColPred
+    a_bits / b_bits).  Nothing is cast silently: a float on an integer
+    column, a negative constant on u64, an integer outside the type's range
+    or one a double cannot hold exactly are errors."""
+    is_bool = isinstance(value, (bool, np.bool_))
+    is_int = isinstance(value, (int, np.integer)) and not is_bool
+    is_float = isinstance(value, (float, np.floating))
+    if not (is_bool or is_int or is_float):
+        raise TypeError(f"predicate constant {value!r} is no int, float or "
+                        "bool")
+    if ctype == CT_F64:
+        if is_bool:
+            raise TypeError("bool constant on an f64 column")
+        if is_int and int(float(value)) != int(value):
+            raise ValueError(f"{value} is not exact in f64")
+        return int(np.array([value], dtype=np.float64).view(np.uint64)[0])
+    if is_float:
+        raise TypeError(f"float constant {value!r} on an integer or bool "
+                        "column: compare in the column's own type")
+    if ctype == CT_BOOL:
+        if int(value) not in (0, 1):
+            raise ValueError(f"bool constant must be 0 or 1, not {value}")
+        return int(value)
+    if is_bool:
+        raise TypeError("bool constant on an integer column")
+    value = int(value)
+    if ctype == CT_I64:
+        if not -2**63 <= value < 2**63:
+            raise OverflowError(f"{value} is outside i64")
+        return value & (2**64 - 1)
+    if ctype == CT_U64:
+        if value < 0:
+            raise ValueError(f"negative constant {value} on a u64 column")
+        if value >= 2**64:
+            raise OverflowError(f"{value} is outside u64")
+        return value
+    raise ValueError(f"no predicate constants for ctype {ctype}")
+
+
 # GsPageInfo as numpy sees it; min/max are re-viewed per column type
 _PAGE_INFO_DT = np.dtype([("len", "<i8"), ("null_count", "<i8"),
                           ("min", "<u8"), ("max", "<u8")])
@@ -233,6 +306,15 @@ class PageLib:
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
             ctypes.POINTER(GsStrColumnOut), ctypes.c_void_p,
             ctypes.POINTER(ctypes.c_int64)]
+        lib.gs_filter_group.restype = ctypes.c_int32
+        lib.gs_filter_group.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.POINTER(GsFilterSpec), ctypes.c_int32,
+            ctypes.POINTER(GsFilterCol), ctypes.c_int32,
+            ctypes.POINTER(GsFilterStrCol), ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_int64)]
+        lib.gs_debug_filter_tile.restype = ctypes.c_int32
+        lib.gs_debug_filter_ms.restype = ctypes.c_float
         lib.gs_debug_set_grid_cap.restype = ctypes.c_int32
         lib.gs_debug_set_grid_cap.argtypes = [ctypes.c_int32]
         lib.gs_debug_grid_rounds.restype = ctypes.c_int32
@@ -696,6 +778,114 @@ class Engine:
             raise e
         return rows.value, offs, totals
 
+    def filter_group(self, gset, d_ts, cols, preds, str_cols=(),
+                     time_range=None, row_tombstones=(), d_out_ts=None):
+        """DataFilter over a column group (gs_filter_group): one mask from
+        the time range, the row tombstones and a conjunction of typed
+        predicates, and every projected column compacted by it.
+
+        cols[c] = (ctype, d_val, d_valid, tombstones, d_out_val,
+        d_out_valid); everything after d_val may be left out or None
+        (d_out_val None = the column only serves predicates).
+        str_cols[s] = ((d_offsets, d_bytes, d_valid), tombstones, out) in
+        decode_str's layout, out = (d_offsets, d_bytes, d_valid) or None.
+        preds = [(col, op, a[, b])], op one of FILTER_OPS ("gt" ... "between",
+        "is_null", "is_not_null"), col >= len(cols) naming a string column;
+        the constants are Python ints, floats or bools, converted to raw
+        bits in the column's own type by pred_bits, which refuses what does
+        not fit.  Tombstones are lists of closed (min_ts, max_ts).
+
+        Returns (out_rows, offsets ndarray of ngroups + 1); the byte totals
+        of the projected string columns are left in self.filter_str_totals
+        (None for a column without output).  The exception of a failed call
+        carries .status (GsStatus), and for GS_ERR_CAP .total_bytes,
+        .out_rows and .offsets: size the byte buffers and call again."""
+        ncols, nstr = len(cols), len(str_cols)
+        keep = []
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        def ranges(lst):
+            lst = list(lst) if lst is not None else []
+            if not lst:
+                return None, 0
+            arr = (GsTimeRange * len(lst))(*[GsTimeRange(a, b) for a, b in lst])
+            keep.append(arr)
+            return arr, len(lst)
+
+        fcols = (GsFilterCol * max(ncols, 1))()
+        ctypes_of = []
+        for c, col in enumerate(cols):
+            col = tuple(col) + (None,) * (6 - len(col))
+            ct, d_val, d_valid, tombs, d_out_val, d_out_valid = col
+            ctypes_of.append(int(ct))
+            fcols[c].ctype = int(ct)
+            fcols[c].d_val = ptr(d_val)
+            fcols[c].d_valid = ptr(d_valid)
+            tarr, tn = ranges(tombs)
+            if tn:
+                fcols[c].tombstones = tarr
+            fcols[c].n_tombstones = tn
+            fcols[c].d_out_val = ptr(d_out_val)
+            fcols[c].d_out_valid = ptr(d_out_valid)
+        fstrs = (GsFilterStrCol * max(nstr, 1))()
+        souts = []
+        for s, col in enumerate(str_cols):
+            col = tuple(col) + (None,) * (3 - len(col))
+            (d_off, d_bytes, d_valid), tombs, out = col
+            fstrs[s].in_ = GsStrColumn(ptr(d_off), ptr(d_bytes), ptr(d_valid))
+            tarr, tn = ranges(tombs)
+            if tn:
+                fstrs[s].tombstones = tarr
+            fstrs[s].n_tombstones = tn
+            if out is None:
+                souts.append(None)
+                continue
+            o = GsStrColumnOut(ptr(out[0]), ptr(out[1]),
+                               out[1].numel() if out[1] is not None else 0,
+                               ptr(out[2]) if len(out) > 2 else None, -1)
+            souts.append(o)
+            fstrs[s].out = ctypes.pointer(o)
+        parr = (GsColPred * max(len(preds), 1))()
+        for p, pred in enumerate(preds):
+            col, op = int(pred[0]), pred[1]
+            parr[p].col = col
+            parr[p].op = FILTER_OPS[op] if isinstance(op, str) else int(op)
+            # constants of a column the library will refuse stay 0
+            if 0 <= col < ncols and ctypes_of[col] in (CT_I64, CT_F64,
+                                                       CT_BOOL, CT_U64):
+                if len(pred) > 2:
+                    parr[p].a_bits = pred_bits(ctypes_of[col], pred[2])
+                if len(pred) > 3:
+                    parr[p].b_bits = pred_bits(ctypes_of[col], pred[3])
+        spec = GsFilterSpec()
+        lo, hi = time_range if time_range else (-(2**63), 2**63 - 1)
+        spec.range = GsTimeRange(lo, hi)
+        tarr, tn = ranges(row_tombstones)
+        if tn:
+            spec.row_tombstones = tarr
+        spec.n_row_tombstones = tn
+        if preds:
+            spec.preds = parr
+        spec.npreds = len(preds)
+        offs = np.zeros(gset.ngroups + 1, dtype=np.int64)
+        rows = ctypes.c_int64(0)
+        st = self.lib.gs_filter_group(
+            self._ctx, gset._h, ptr(d_ts), ctypes.byref(spec), ncols,
+            fcols if ncols else None, nstr, fstrs if nstr else None,
+            ptr(d_out_ts), _np_ptr(offs), ctypes.byref(rows))
+        self.filter_str_totals = [
+            int(o.total_bytes) if o is not None else None for o in souts]
+        if st != 0:
+            e = RuntimeError(
+                f"gs_filter_group failed ({st}): {self._pl.err()}")
+            e.status = st
+            e.total_bytes = self.filter_str_totals
+            e.out_rows, e.offsets = rows.value, offs
+            raise e
+        return rows.value, offs
+
     def encode_pages_dev(self, kind, d_vals, row_off, rows, d_out,
                          cap_per_page, d_valid=None):
         """GPU page re-encode. kind: 0=ts 1=i64 2=f64. row_off/rows: host
@@ -1055,6 +1245,18 @@ def scan_fields_async(engine, gset, fields, d_ts, d_val, time_range,
     if st != 0:
         raise RuntimeError(
             f"gs_scan_fields_async failed ({st}): {engine._pl.err()}")
+
+
+def filter_tile():
+    """FLT_TILE: rows per block of gs_filter_group's kernels (four waves of
+    FLT_TILE / 4 rows each), for the tests' edge sizes."""
+    return int(PageLib().lib.gs_debug_filter_tile())
+
+
+def filter_ms():
+    """Device time of the last filter_group call, first to last kernel,
+    from HIP events on the engine stream (gs_debug_filter_ms)."""
+    return float(PageLib().lib.gs_debug_filter_ms())
 
 
 def grid_rounds(reset=False):

@@ -540,6 +540,109 @@ GsStatus gs_compact_merge_group(
     GsStrColumnOut *str_out,                   /* [nstr] */
     int64_t *h_out_offsets, int64_t *out_rows);
 
+/* ---- DataFilter over a column group: multi-column predicates ----
+ * The reference's DataFilter (tskv/src/reader/filter.rs:91-142) evaluates
+ * ONE pushed expression over the whole RecordBatch and filters every
+ * projected column with the resulting mask; decode_pages
+ * (tsm/reader.rs:494-560) has applied the tombstones before that: ranges
+ * that exclude all fields remove the row (time_null_bits, then
+ * filter_record_batch), per-column ranges null that column's cells.
+ * gs_filter_group is both steps over decoded columns exactly as gs_decode
+ * and gs_decode_str leave them (the convention of gs_compact_merge_fields;
+ * a raw set, gs_raw_set, works like a page set): one mask from a
+ * conjunction of typed predicates over any of the group's columns, and
+ * every projected column compacted by that mask, with its validity.
+ *
+ * Tombstone ranges.  Every range is closed: a row is inside iff
+ * min_ts <= ts <= max_ts, which on strictly increasing timestamps is
+ * update_nullbits_by_time_range (tsm/reader.rs:634-656).  A list may be
+ * unsorted and overlapping; a range with min_ts > max_ts matches nothing.
+ * Ranges apply to every group of the set, as in gs_apply_tombstone.
+ *
+ * Effective validity of cell (r, c) = valid[c][r] AND ts[r] lies in none of
+ * column c's ranges.  Predicates and outputs both see the effective
+ * validity, never the raw one.
+ *
+ * Keep rule.  Row r is kept iff ts[r] is in spec->range, ts[r] is in no row
+ * tombstone, and every predicate holds.  A comparison on an effectively
+ * null cell fails (arrow's comparison with null is null, and
+ * filter_record_batch treats null as false).  GS_PRED_IS_NULL and
+ * GS_PRED_IS_NOT_NULL test the effective validity and never read the value.
+ *
+ * Comparisons run in the column's own type, on the constant's raw bits:
+ * i64 signed, u64 unsigned, bool as 0/1, so `x >= 2^53 + 1` on an i64
+ * column and a u64 bound above 2^63 mean what they say.  f64 compares with
+ * the IEEE operators exactly as gs_scan's value predicate does: NaN fails
+ * everything but NE, and -0.0 == +0.0; the two entries agree on every
+ * input.  Whether arrow 42's comparison kernels order NaN and signed zero
+ * the same way is NOT VERIFIED here; no parity with the reference is
+ * claimed on those two inputs.
+ *
+ * Outputs.  Kept rows stay in input order.  h_out_offsets[g] is the output
+ * row at which group g's rows start, h_out_offsets[gs_set_groups] ==
+ * *out_rows.  A projected cell that is effectively null has all-zero value
+ * bytes and validity 0, like gs_compact_merge_fields, whatever its input
+ * slot held: the output is bit-comparable.  A projected string column is
+ * Arrow varbinary in GsStrColumnOut (d_offsets holds gs_set_rows + 1
+ * entries); a null cell has length 0, and bytes of null input rows are
+ * never read.  A column with d_out_val == NULL (out == NULL for a string
+ * column) only serves predicates.  GS_ERR_CAP when a string column's
+ * total_bytes exceeds its bytes_cap: every total_bytes is filled, no
+ * d_bytes of any column is written and everything else is as on success
+ * (the gs_compact_merge_group protocol: size the buffers, call again).
+ *
+ * GS_ERR (with a message, before any device work) for ncols + nstr outside
+ * 1..GS_MAX_MERGE_COLS, npreds outside 0..GS_MAX_FILTER_PREDS, a ctype
+ * other than the four fixed-width types, a predicate whose col is out of
+ * range, a comparison op on a string column, an unknown op, a NULL
+ * required pointer, or a string column with more than 2^28 rows in the set
+ * (the device scan's limit).  A failed call leaves the context usable.
+ * gs_scan does not take the two null tests. */
+#define GS_MAX_FILTER_PREDS 16
+enum { GS_PRED_IS_NULL = 8, GS_PRED_IS_NOT_NULL = 9 }; /* gs_filter_group only */
+
+typedef struct {
+    int32_t col;      /* 0..ncols-1 = cols[col]; ncols+s = string column s
+                         (IS_NULL / IS_NOT_NULL only) */
+    int32_t op;       /* GS_PRED_GT..GS_PRED_BETWEEN, IS_NULL, IS_NOT_NULL */
+    uint64_t a_bits;  /* the constant in the COLUMN'S OWN TYPE, raw bits:
+                         f64 bits, i64, u64, bool 0/1 */
+    uint64_t b_bits;  /* BETWEEN upper bound (closed) */
+} GsColPred;
+
+typedef struct {
+    uint8_t ctype;                  /* GS_CT_I64 / F64 / BOOL / U64 */
+    const void *d_val;              /* 8 B/row, bool 1 B/row */
+    const uint8_t *d_valid;         /* NULL = all valid */
+    const GsTimeRange *tombstones;  /* host; this column's deleted ranges */
+    size_t n_tombstones;
+    void *d_out_val;                /* NULL = predicate-only, not projected */
+    uint8_t *d_out_valid;           /* may be NULL */
+} GsFilterCol;
+
+typedef struct {
+    GsStrColumn in;                 /* as gs_decode_str leaves it */
+    const GsTimeRange *tombstones;
+    size_t n_tombstones;
+    GsStrColumnOut *out;            /* NULL = not projected */
+} GsFilterStrCol;
+
+typedef struct {
+    GsTimeRange range;                    /* closed */
+    const GsTimeRange *row_tombstones;    /* all-fields ranges: row removed */
+    size_t n_row_tombstones;
+    const GsColPred *preds;               /* conjunction; npreds 0 = none */
+    int32_t npreds;
+} GsFilterSpec;
+
+GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
+                         const GsFilterSpec *spec,
+                         int32_t ncols, const GsFilterCol *cols,
+                         int32_t nstr, const GsFilterStrCol *strs,
+                         int64_t *d_out_ts,      /* >= gs_set_rows rows */
+                         int64_t *h_out_offsets, /* [gs_set_groups + 1] */
+                         int64_t *out_rows);
+
 /* ---- Arrow C Data Interface export (decode output as
  * ArrowArray so the Rust shim reconstitutes RecordBatches zero-copy from
  * the shim's side).  GsArrowArray is layout-identical to `struct
