@@ -33,6 +33,7 @@ from .host import (
     pred_bits,
     filter_tile,
     filter_ms,
+    agg_ms,
     FILTER_OPS,
     CT_TIME,
     CT_I64,
@@ -47,7 +48,7 @@ __all__ = [
     "encode_ts", "encode_i64", "encode_f64", "encode_bool", "encode_str",
     "build_page", "crc32", "page_of", "str_page_of", "prune_column_groups", "fold_page_stats", "groupby_tag", "scan_fields", "scan_fields_async",
     "grid_cap", "grid_rounds",
-    "pred_bits", "filter_tile", "filter_ms", "FILTER_OPS",
+    "pred_bits", "filter_tile", "filter_ms", "agg_ms", "FILTER_OPS",
     "CT_TIME", "CT_I64", "CT_F64", "CT_BOOL", "CT_U64", "CT_STR",
 ]
 __version__ = "0.1"

@@ -22,6 +22,7 @@
 #include "gs_int_dec.h"
 #include "gs_str_enc.h"
 #include "gs_filter.h"
+#include "gs_agg.h"
 
 /* hipError_t returns are checked with HIP_TRY on every path that can fail
  * user-visibly; cleanup paths (hipFree/hipEventDestroy in destructors) and
@@ -3009,6 +3010,27 @@ __device__ __forceinline__ bool flt_effective(const FltCol &c,
     return !(c.rng_cnt && flt_in_ranges(ranges + c.rng_off, c.rng_cnt, t));
 }
 
+/* the keep rule of row r with timestamp t: the time range, the row
+   tombstones and the conjunction (gs_filter_group and gs_agg_group) */
+__device__ __forceinline__ bool flt_keep(const FltMaskArgs &a, int64_t r,
+                                         int64_t t) {
+    bool keep = t >= a.lo && t <= a.hi &&
+                !(a.row_rng_cnt && flt_in_ranges(a.ranges, a.row_rng_cnt, t));
+    for (int p = 0; p < a.npreds; p++) {
+        if (!keep) break;
+        const FltCol &c = a.pcol[p];
+        const int op = a.pred[p].op;
+        const bool ev = flt_effective(c, a.ranges, r, t);
+        uint64_t x = 0;
+        if (ev && !flt_op_is_null_test(op))
+            x = c.ctype == GS_CT_BOOL ? uint64_t(((const uint8_t *)c.val)[r])
+                                      : ((const uint64_t *)c.val)[r];
+        keep = flt_cell(op, c.ctype, a.pred[p].a_bits, a.pred[p].b_bits, x,
+                        ev);
+    }
+    return keep;
+}
+
 /* mask[r] = the keep rule; seg_cnt[seg] = kept rows of the wave's segment */
 __global__ __launch_bounds__(256) void k_flt_mask(
     FltMaskArgs a, int64_t nseg, uint8_t *__restrict__ mask,
@@ -3023,23 +3045,7 @@ __global__ __launch_bounds__(256) void k_flt_mask(
             const int64_t r = seg * FLT_SEG + s * 64 + lane;
             bool keep = false;
             if (r < a.rows) {
-                const int64_t t = a.ts[r];
-                keep = t >= a.lo && t <= a.hi &&
-                       !(a.row_rng_cnt &&
-                         flt_in_ranges(a.ranges, a.row_rng_cnt, t));
-                for (int p = 0; p < a.npreds; p++) {
-                    if (!keep) break;
-                    const FltCol &c = a.pcol[p];
-                    const int op = a.pred[p].op;
-                    const bool ev = flt_effective(c, a.ranges, r, t);
-                    uint64_t x = 0;
-                    if (ev && !flt_op_is_null_test(op))
-                        x = c.ctype == GS_CT_BOOL
-                                ? uint64_t(((const uint8_t *)c.val)[r])
-                                : ((const uint64_t *)c.val)[r];
-                    keep = flt_cell(op, c.ctype, a.pred[p].a_bits,
-                                    a.pred[p].b_bits, x, ev);
-                }
+                keep = flt_keep(a, r, a.ts[r]);
                 mask[r] = keep;
             }
             cnt += __popcll(__ballot(keep));
@@ -3117,6 +3123,348 @@ __global__ void k_flt_group_off(const DevGroup *__restrict__ groups, int ng,
             v = seg_off[seg] + c;
         }
         if (lane == 0) out_off[g] = v;
+    }
+}
+
+/* --------------------------------------- column-group aggregate kernels
+ * gs_agg_group: the keep rule of gs_filter_group, reduced straight into
+ * (series, bucket) cells.  Rows of a series are contiguous, series ascend
+ * along the row space and buckets along a sorted series, so the cell KEY
+ * series * n_buckets + slot (agg_bucket's slot: a row in no bucket sorts
+ * next to the bucket beside it and contributes nothing) never decreases and
+ * every cell is ONE run of consecutive rows.  The work item is the filter's
+ * wave segment of FLT_SEG rows, whatever the series or bucket sizes:
+ *
+ *   k_agg_init     the empty-cell values into every requested array
+ *   k_agg_seg      pass A, once per segment: timestamp, keep rule, series,
+ *                  slot and key of every row, and the sorted check; pass B,
+ *                  once per aggregated column: a segmented reduction over
+ *                  the runs of the segment.  While whole 64-row steps stay
+ *                  inside the open run each lane folds its own rows and no
+ *                  lane talks to another; a step in which the key changes is
+ *                  folded by a segmented scan over the lanes (run heads =
+ *                  "key differs from the lane before").  Runs that begin
+ *                  and end inside the segment are written to their cell; the
+ *                  first and the last run go to the segment's two carry
+ *                  records
+ *   k_agg_stitch   one wave per (run of equal carry keys, column): folds
+ *                  the records of a run that crosses segments, however many,
+ *                  and writes its cell
+ *   k_agg_fold     per_series == 0 only: the (series, bucket) partials are
+ *                  kept whole in scratch and one wave per (bucket, column)
+ *                  folds them over the series
+ *
+ * No value is ever added atomically and nothing depends on which block ran
+ * first: which rows meet in which fold is fixed by the segment geometry
+ * alone, so an f64 sum has the same bits under any grid.  agg_combine is
+ * commutative by its row indices (gs_agg.h), which is what lets a lane fold
+ * rows 64 apart and a butterfly fold the lanes.  Pass A keeps its per-row
+ * results in LDS as a lane-private array (no barrier: no lane reads
+ * another's slot), so pass B is one compact loop, not eight unrolled
+ * copies. */
+struct AggCol {              /* one aggregated column; ctype GS_CT_TIME and
+                                val NULL: the kept-row counter (d_rows) */
+    FltCol c;
+    int64_t *o_count;
+    uint64_t *o_sum, *o_mn, *o_mx, *o_first, *o_last;
+    int64_t *o_first_ts, *o_last_ts;
+};
+
+struct AggGeom {
+    const DevGroup *sg;      /* series-level groups */
+    int32_t nsg;
+    int32_t nb;
+    int64_t t0, bn;
+    int32_t ncol;            /* aggregated columns (+ 1 for d_rows) */
+    int32_t pad;
+    uint64_t *scratch;       /* per_series == 0: [ncol][AGG_NFIELD][scells] */
+    int64_t scells;          /* nsg * nb */
+    int64_t *ckey;           /* [nrec] carry keys: 2 * seg head, + 1 tail */
+    uint64_t *ctab;          /* [ncol][AGG_NFIELD][nrec] carry partials */
+    int64_t nrec;
+};
+
+__device__ __forceinline__ uint64_t agg_shfl64(uint64_t v, int src) {
+    const uint32_t lo = __shfl(uint32_t(v), src, 64);
+    const uint32_t hi = __shfl(uint32_t(v >> 32), src, 64);
+    return (uint64_t(hi) << 32) | lo;
+}
+
+__device__ __forceinline__ AggPart agg_shfl(const AggPart &p, int src) {
+    uint64_t w[AGG_NFIELD];
+    __builtin_memcpy(w, &p, sizeof(AggPart));
+#pragma unroll
+    for (int f = 0; f < AGG_NFIELD; f++) w[f] = agg_shfl64(w[f], src);
+    AggPart o;
+    __builtin_memcpy(&o, w, sizeof(AggPart));
+    return o;
+}
+
+/* fold over the 64 lanes; every lane ends with the same bits */
+__device__ __forceinline__ AggPart agg_wave_fold(int ct, AggPart p, int lane) {
+    for (int off = 32; off > 0; off >>= 1)
+        p = agg_combine(ct, p, agg_shfl(p, lane ^ off));
+    return p;
+}
+
+__device__ __forceinline__ void agg_tab_store(uint64_t *tab, int64_t n, int k,
+                                              int64_t i, const AggPart &p) {
+    uint64_t w[AGG_NFIELD];
+    __builtin_memcpy(w, &p, sizeof(AggPart));
+#pragma unroll
+    for (int f = 0; f < AGG_NFIELD; f++)
+        tab[(int64_t(k) * AGG_NFIELD + f) * n + i] = w[f];
+}
+
+__device__ __forceinline__ AggPart agg_tab_load(const uint64_t *tab, int64_t n,
+                                                int k, int64_t i) {
+    uint64_t w[AGG_NFIELD];
+#pragma unroll
+    for (int f = 0; f < AGG_NFIELD; f++)
+        w[f] = tab[(int64_t(k) * AGG_NFIELD + f) * n + i];
+    AggPart o;
+    __builtin_memcpy(&o, w, sizeof(AggPart));
+    return o;
+}
+
+/* a finished cell into the caller's arrays */
+__device__ __forceinline__ void agg_write_out(const AggCol &c, int64_t cell,
+                                              const AggPart &p) {
+    if (c.o_count) c.o_count[cell] = p.count;
+    if (c.o_sum) c.o_sum[cell] = p.sum;
+    if (c.o_mn) c.o_mn[cell] = p.mn;
+    if (c.o_mx) c.o_mx[cell] = p.mx;
+    if (c.o_first) c.o_first[cell] = p.first;
+    if (c.o_last) c.o_last[cell] = p.last;
+    if (c.o_first_ts) c.o_first_ts[cell] = p.first_ts;
+    if (c.o_last_ts) c.o_last_ts[cell] = p.last_ts;
+}
+
+/* a finished (series, bucket) run: to the caller's arrays, or whole into the
+   scratch that k_agg_fold reduces over the series */
+__device__ __forceinline__ void agg_emit(const AggGeom &g, const AggCol &c,
+                                         int k, int64_t key, const AggPart &p) {
+    if (g.scratch)
+        agg_tab_store(g.scratch, g.scells, k, key, p);
+    else
+        agg_write_out(c, key, p);
+}
+
+/* the last series in [lo, hi) that starts at or before row r; series without
+   rows share their start with the next one that has some, which is the last
+   of them, so the answer always holds r.  Needs sg[lo].row_off <= r. */
+__device__ __forceinline__ int agg_series_of(const DevGroup *sg, int lo, int hi,
+                                             int64_t r) {
+    while (hi - lo > 1) {
+        const int m = lo + ((hi - lo) >> 1);
+        if (sg[m].row_off <= r) lo = m; else hi = m;
+    }
+    return lo;
+}
+
+__global__ void k_agg_init(AggGeom g, const AggCol *__restrict__ cols,
+                           int64_t ncell) {
+    const int64_t n = g.scratch ? g.scells : ncell;
+    const int64_t step = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n;
+         i += step)
+        for (int k = 0; k < g.ncol; k++)
+            agg_emit(g, cols[k], k, i, agg_empty(cols[k].c.ctype));
+}
+
+__global__ __launch_bounds__(256) void k_agg_seg(
+    FltMaskArgs a, AggGeom g, const AggCol *__restrict__ cols, int64_t nseg,
+    unsigned *__restrict__ err) {
+    /* lane-private [step][thread]: no lane reads another's slot */
+    __shared__ int64_t s_ts[FLT_SEG / 64][256];
+    __shared__ int64_t s_key[FLT_SEG / 64][256];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int64_t ntile = (nseg + 3) / 4;
+    for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+        const int64_t seg = tile * 4 + wave;
+        if (seg >= nseg) continue; /* wave-uniform; no barrier below */
+        const int64_t r0 = seg * FLT_SEG;
+        const int64_t left = a.rows - r0; /* >= 1 */
+        const int nstep = left >= FLT_SEG ? FLT_SEG / 64 : int((left + 63) >> 6);
+
+        /* ---- pass A: every row's timestamp, key and "contributes" bit.
+           Lanes behind the last row repeat it and contribute nothing. */
+        uint32_t cbits = 0;
+        int s_cur = __builtin_amdgcn_readfirstlane(
+            agg_series_of(g.sg, 0, g.nsg, r0));
+        bool w_ok = false; /* bucket window of the last row of the step before */
+        uint64_t w_lo = 0, w_b = 0;
+        int64_t prev63 = r0 > 0 ? a.ts[r0 - 1] : 0;
+        for (int s = 0; s < nstep; s++) {
+            const int64_t r = r0 + s * 64 + lane;
+            const bool in = r < a.rows;
+            const int64_t rc = in ? r : a.rows - 1;
+            const int64_t r_hi = r0 + s * 64 + 63 < a.rows ? r0 + s * 64 + 63
+                                                           : a.rows - 1;
+            const int64_t t = a.ts[rc];
+            /* series: from the table only in a step a boundary falls in */
+            int ser = s_cur;
+            if (s_cur + 1 < g.nsg && g.sg[s_cur + 1].row_off <= r_hi) {
+                int hi = s_cur + 65 < g.nsg ? s_cur + 65 : g.nsg;
+                if (hi < g.nsg && g.sg[hi].row_off <= r_hi) hi = g.nsg;
+                ser = agg_series_of(g.sg, s_cur, hi, rc);
+            }
+            s_cur = __builtin_amdgcn_readlane(ser, 63);
+            /* sorted inside the series: a compare with the row before */
+            const int64_t up =
+                int64_t(agg_shfl64(uint64_t(t), lane ? lane - 1 : 0));
+            const int64_t prev = lane ? up : prev63;
+            if (in && r > g.sg[ser].row_off && t <= prev)
+                atomicOr(err, DERR_NONMONO);
+            prev63 = int64_t(agg_shfl64(uint64_t(t), 63));
+            /* bucket: the window carried from the step before answers for
+               the same and the next bucket; only other rows divide */
+            uint64_t b = 0;
+            bool before = false;
+            if (g.bn != 0) {
+                before = t < g.t0;
+                const uint64_t d = uint64_t(t) - uint64_t(g.t0);
+                if (!before &&
+                    !(w_ok && agg_bucket_near(d, w_lo, w_b, uint64_t(g.bn), &b)))
+                    agg_bucket_raw(t, g.t0, g.bn, &b);
+            }
+            int32_t slot = 0;
+            const bool inb = !before && agg_slot(b, g.nb, &slot);
+            w_ok = g.bn != 0 && !__shfl(int(before), 63, 64);
+            w_b = agg_shfl64(b, 63);
+            w_lo = w_b * uint64_t(g.bn); /* <= ts - t0: no overflow */
+            s_ts[s][tid] = t;
+            s_key[s][tid] = int64_t(ser) * g.nb + slot;
+            if (in && inb && flt_keep(a, r, t)) cbits |= 1u << s;
+        }
+
+        /* ---- pass B: column by column over the stored steps */
+        const int64_t key_first = agg_shfl64(uint64_t(s_key[0][tid]), 0);
+        for (int k = 0; k < g.ncol; k++) {
+            const AggCol col = cols[k];
+            const int ct = col.c.ctype;
+            AggPart acc = agg_empty(ct);  /* this lane's rows of the open run */
+            AggPart open = agg_empty(ct); /* the open run before those */
+            int64_t open_key = key_first;
+            bool open_is_first = true;
+            for (int s = 0; s < nstep; s++) {
+                const int64_t r = r0 + s * 64 + lane;
+                const int64_t t = s_ts[s][tid];
+                const int64_t key = s_key[s][tid];
+                AggPart me = agg_empty(ct);
+                if ((cbits >> s) & 1) {
+                    if (!col.c.val) {
+                        me = agg_single(ct, 0, t, r);
+                    } else if (flt_effective(col.c, a.ranges, r, t)) {
+                        const uint64_t x =
+                            ct == GS_CT_BOOL
+                                ? uint64_t(((const uint8_t *)col.c.val)[r])
+                                : ((const uint64_t *)col.c.val)[r];
+                        me = agg_single(ct, x, t, r);
+                    }
+                }
+                const int64_t k0 = agg_shfl64(uint64_t(key), 0);
+                const int64_t k63 = agg_shfl64(uint64_t(key), 63);
+                if (k0 == open_key && k63 == open_key) { /* wave-uniform */
+                    acc = agg_combine(ct, acc, me);
+                    continue;
+                }
+                /* the key changes in this step: segmented inclusive scan */
+                AggPart sc = me;
+                for (int off = 1; off < 64; off <<= 1) {
+                    const int src = lane >= off ? lane - off : lane;
+                    const AggPart o = agg_shfl(sc, src);
+                    const int64_t ko = agg_shfl64(uint64_t(key), src);
+                    if (lane >= off && ko == key) sc = agg_combine(ct, o, sc);
+                }
+                /* close the open run: what came before, the lanes' own rows,
+                   and the leading lanes of this step that still belong to it */
+                AggPart tot = agg_combine(ct, open, agg_wave_fold(ct, acc, lane));
+                const int p = __popcll(__ballot(key == open_key));
+                if (p > 0) tot = agg_combine(ct, tot, agg_shfl(sc, p - 1));
+                if (lane == 0) {
+                    if (open_is_first) {
+                        g.ckey[2 * seg] = open_key;
+                        agg_tab_store(g.ctab, g.nrec, k, 2 * seg, tot);
+                    } else {
+                        agg_emit(g, col, k, open_key, tot);
+                    }
+                }
+                open_is_first = false;
+                /* runs that end inside this step and are not the open one */
+                const int nxt = lane < 63 ? lane + 1 : lane;
+                const int64_t kn = agg_shfl64(uint64_t(key), nxt);
+                if (lane < 63 && kn != key && key != open_key)
+                    agg_emit(g, col, k, key, sc);
+                /* the run that reaches the step's end is the open one now */
+                open = agg_shfl(sc, 63);
+                open_key = k63;
+                acc = agg_empty(ct);
+            }
+            const AggPart tot =
+                agg_combine(ct, open, agg_wave_fold(ct, acc, lane));
+            if (lane == 0) {
+                /* one run over the whole segment: the tail record is the
+                   same key with nothing in it */
+                g.ckey[2 * seg + 1] = open_key;
+                if (open_is_first) {
+                    g.ckey[2 * seg] = open_key;
+                    agg_tab_store(g.ctab, g.nrec, k, 2 * seg, tot);
+                    agg_tab_store(g.ctab, g.nrec, k, 2 * seg + 1,
+                                  agg_empty(ct));
+                } else {
+                    agg_tab_store(g.ctab, g.nrec, k, 2 * seg + 1, tot);
+                }
+            }
+        }
+    }
+}
+
+/* Carry keys never decrease, so the records of one cell are consecutive.
+   One wave per (record that starts a run of equal keys, column): the lanes
+   fold records 64 apart, a butterfly folds the lanes, lane 0 writes the
+   cell.  The shape of the fold depends on the run alone. */
+__global__ __launch_bounds__(256) void k_agg_stitch(
+    AggGeom g, const AggCol *__restrict__ cols) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t(gridDim.x) * blockDim.x) >> 6;
+    const int64_t items = g.nrec * g.ncol;
+    for (int64_t it = (blockIdx.x * int64_t(blockDim.x) + threadIdx.x) >> 6;
+         it < items; it += nw) {
+        const int64_t rec = it / g.ncol;
+        const int k = int(it - rec * g.ncol);
+        const int64_t key = g.ckey[rec];
+        if (rec > 0 && g.ckey[rec - 1] == key) continue; /* wave-uniform */
+        const AggCol col = cols[k];
+        const int ct = col.c.ctype;
+        AggPart acc = agg_empty(ct);
+        for (int64_t i = rec + lane; i < g.nrec && g.ckey[i] == key; i += 64)
+            acc = agg_combine(ct, acc, agg_tab_load(g.ctab, g.nrec, k, i));
+        acc = agg_wave_fold(ct, acc, lane);
+        if (lane == 0) agg_emit(g, col, k, key, acc);
+    }
+}
+
+/* per_series == 0: cell b of column k = the fold of scratch cells
+   (s, b) over the series, one wave per (bucket, column) */
+__global__ __launch_bounds__(256) void k_agg_fold(
+    AggGeom g, const AggCol *__restrict__ cols) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t(gridDim.x) * blockDim.x) >> 6;
+    const int64_t items = int64_t(g.nb) * g.ncol;
+    for (int64_t it = (blockIdx.x * int64_t(blockDim.x) + threadIdx.x) >> 6;
+         it < items; it += nw) {
+        const int64_t b = it / g.ncol;
+        const int k = int(it - b * g.ncol);
+        const AggCol col = cols[k];
+        const int ct = col.c.ctype;
+        AggPart acc = agg_empty(ct);
+        for (int64_t s = lane; s < g.nsg; s += 64)
+            acc = agg_combine(ct, acc, agg_tab_load(g.scratch, g.scells, k,
+                                                    s * g.nb + b));
+        acc = agg_wave_fold(ct, acc, lane);
+        if (lane == 0) agg_write_out(col, b, acc);
     }
 }
 
@@ -3254,6 +3602,14 @@ struct GsGroupSet {
     size_t flt_ranges_cap = 0;
     uint64_t *d_flt_ref = nullptr;
     size_t flt_ref_cap = 0;
+    /* gs_agg_group scratch (lazy, cached across calls, sizes in 8-byte
+       words): the segments' carry keys and partials; the column table; the
+       (series, bucket) partials of a per_series == 0 call */
+    uint64_t *d_agg_carry = nullptr;
+    size_t agg_carry_cap = 0;
+    void *d_agg_cols = nullptr;
+    uint64_t *d_agg_scr = nullptr;
+    size_t agg_scr_cap = 0;
     int64_t *d_sel_cnt = nullptr; /* per-group masked selected counts (lazy) */
     bool any_nulls_field = false;
     /* agg partials: ngroups x nbuckets cells, cached across scans */
@@ -3780,6 +4136,9 @@ void gs_groups_free(GsGroupSet *set) {
     if (set->d_flt_seg) hipFree(set->d_flt_seg);
     if (set->d_flt_ranges) hipFree(set->d_flt_ranges);
     if (set->d_flt_ref) hipFree(set->d_flt_ref);
+    if (set->d_agg_carry) hipFree(set->d_agg_carry);
+    if (set->d_agg_cols) hipFree(set->d_agg_cols);
+    if (set->d_agg_scr) hipFree(set->d_agg_scr);
     if (set->d_sel_cnt) hipFree(set->d_sel_cnt);
     if (set->d_pmax) hipFree(set->d_pmax);
     if (set->d_psum) hipFree(set->d_psum);
@@ -5478,17 +5837,29 @@ float gs_debug_filter_ms(void) {
 /* debug: rows per block of the filter kernels, for the tests' edge sizes */
 int32_t gs_debug_filter_tile(void) { return FLT_TILE; }
 
-GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
-                         const GsFilterSpec *spec, int32_t ncols,
-                         const GsFilterCol *cols, int32_t nstr,
-                         const GsFilterStrCol *strs, int64_t *d_out_ts,
-                         int64_t *h_out_offsets, int64_t *out_rows) {
-    auto bad = [](const char *msg) {
-        return fail(GS_ERR, (std::string("gs_filter_group: ") + msg).c_str());
+} // extern "C"
+
+namespace {
+/* What gs_filter_group and gs_agg_group share in front of their kernels:
+ * the argument checks of the filter and its columns, every range list in
+ * normal form in one table (row tombstones first) and the columns as the
+ * kernels see them.  `who` names the entry in messages; `outputs` is false
+ * for gs_agg_group, which ignores the output fields of the columns. */
+struct FltPlan {
+    std::vector<GsTimeRange> rtab;
+    std::vector<FltCol> fc;   /* [ncols + nstr] */
+    std::vector<int> pstr;    /* projected string columns */
+    int32_t row_cnt = 0;
+    int64_t nseg = 0;
+};
+
+GsStatus flt_plan(const char *who, bool outputs, const GsGroupSet *set,
+                  const GsFilterSpec *spec, int32_t ncols,
+                  const GsFilterCol *cols, int32_t nstr,
+                  const GsFilterStrCol *strs, FltPlan &pl) {
+    auto bad = [who](const char *msg) {
+        return fail(GS_ERR, (std::string(who) + ": " + msg).c_str());
     };
-    if (!ctx || !set || !d_ts || !spec || !d_out_ts || !h_out_offsets ||
-        !out_rows)
-        return bad("NULL argument");
     if (ncols < 0 || nstr < 0 || ncols > GS_MAX_MERGE_COLS ||
         nstr > GS_MAX_MERGE_COLS || ncols + nstr < 1 ||
         ncols + nstr > GS_MAX_MERGE_COLS)
@@ -5513,7 +5884,7 @@ GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
     for (int c = 0; c < nstr; c++) {
         if (strs[c].n_tombstones > 0 && !strs[c].tombstones)
             return bad("NULL column pointer");
-        const GsStrColumnOut *o = strs[c].out;
+        const GsStrColumnOut *o = outputs ? strs[c].out : nullptr;
         if (o && (!strs[c].in.d_offsets || !strs[c].in.d_bytes ||
                   !o->d_offsets || !o->d_bytes || o->bytes_cap < 0))
             return bad("NULL string column pointer");
@@ -5529,14 +5900,15 @@ GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
             return bad("a string column takes IS_NULL / IS_NOT_NULL only");
     }
     const int64_t rows = set->total_rows;
-    const int ng = int(set->ngroups);
-    if (nstr > 0 && rows > (int64_t(1) << 28))
+    if (outputs && nstr > 0 && rows > (int64_t(1) << 28))
         return bad("string column row limit exceeded (2^28)");
-    const int64_t nseg = (rows + FLT_SEG - 1) / FLT_SEG;
-    if (nseg > INT32_MAX / 2) return bad("too many rows for the segment scan");
+    pl.nseg = (rows + FLT_SEG - 1) / FLT_SEG;
+    if (pl.nseg > INT32_MAX / 2)
+        return bad("too many rows for the segment scan");
 
     /* every range list in normal form, one table: row tombstones first */
-    std::vector<GsTimeRange> rtab;
+    std::vector<GsTimeRange> &rtab = pl.rtab;
+    rtab.clear();
     rtab.reserve(nranges_in);
     auto add_list = [&](const GsTimeRange *r, size_t n, int32_t &off,
                         int32_t &cnt) {
@@ -5545,33 +5917,94 @@ GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
         cnt = int32_t(flt_normalise(rtab.data() + off, int64_t(n)));
         rtab.resize(size_t(off) + size_t(cnt));
     };
-    int32_t row_off0 = 0, row_cnt = 0;
-    add_list(spec->row_tombstones, spec->n_row_tombstones, row_off0, row_cnt);
-    std::vector<FltCol> fc(size_t(ncols + nstr));
+    int32_t row_off0 = 0;
+    add_list(spec->row_tombstones, spec->n_row_tombstones, row_off0,
+             pl.row_cnt);
+    std::vector<FltCol> &fc = pl.fc;
+    fc.assign(size_t(ncols + nstr), FltCol());
     for (int c = 0; c < ncols; c++) {
         FltCol &f = fc[c];
         f.val = cols[c].d_val;
         f.valid = cols[c].d_valid;
-        f.out_val = cols[c].d_out_val;
-        f.out_valid = cols[c].d_out_val ? cols[c].d_out_valid : nullptr;
+        f.out_val = outputs ? cols[c].d_out_val : nullptr;
+        f.out_valid = f.out_val ? cols[c].d_out_valid : nullptr;
         f.ctype = cols[c].ctype;
         f.pad = 0;
         add_list(cols[c].tombstones, cols[c].n_tombstones, f.rng_off,
                  f.rng_cnt);
     }
-    std::vector<int> pstr; /* projected string columns */
+    pl.pstr.clear();
     for (int c = 0; c < nstr; c++) {
         FltCol &f = fc[ncols + c];
+        const GsStrColumnOut *o = outputs ? strs[c].out : nullptr;
         f.val = nullptr;
         f.valid = strs[c].in.d_valid;
-        f.out_val = nullptr; /* its reference array, below */
-        f.out_valid = strs[c].out ? strs[c].out->d_valid : nullptr;
+        f.out_val = nullptr; /* its reference array, set by the entry */
+        f.out_valid = o ? o->d_valid : nullptr;
         f.ctype = GS_CT_STR;
         f.pad = 0;
         add_list(strs[c].tombstones, strs[c].n_tombstones, f.rng_off,
                  f.rng_cnt);
-        if (strs[c].out) pstr.push_back(c);
+        if (o) pl.pstr.push_back(c);
     }
+    return GS_OK;
+}
+
+/* the range table into the set's cached device copy, and the mask kernel's
+   arguments; call after hipSetDevice */
+GsStatus flt_mask_args(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
+                       const GsFilterSpec *spec, const FltPlan &pl,
+                       FltMaskArgs &ma) {
+    if (set->flt_ranges_cap < pl.rtab.size()) {
+        if (set->d_flt_ranges) hipFree(set->d_flt_ranges);
+        set->d_flt_ranges = nullptr;
+        set->flt_ranges_cap = 0;
+        HIP_TRY(hipMalloc(&set->d_flt_ranges,
+                          pl.rtab.size() * sizeof(GsTimeRange)));
+        set->flt_ranges_cap = pl.rtab.size();
+    }
+    if (!pl.rtab.empty())
+        HIP_TRY(hipMemcpyAsync(set->d_flt_ranges, pl.rtab.data(),
+                               pl.rtab.size() * sizeof(GsTimeRange),
+                               hipMemcpyHostToDevice, ctx->stream));
+    memset(&ma, 0, sizeof(ma));
+    ma.ts = d_ts;
+    ma.ranges = set->d_flt_ranges;
+    ma.rows = set->total_rows;
+    ma.lo = spec->range.min_ts;
+    ma.hi = spec->range.max_ts;
+    ma.row_rng_cnt = pl.row_cnt;
+    ma.npreds = spec->npreds;
+    for (int p = 0; p < spec->npreds; p++) {
+        ma.pred[p] = spec->preds[p];
+        ma.pcol[p] = pl.fc[spec->preds[p].col];
+    }
+    return GS_OK;
+}
+} // namespace
+
+extern "C" {
+
+GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
+                         const GsFilterSpec *spec, int32_t ncols,
+                         const GsFilterCol *cols, int32_t nstr,
+                         const GsFilterStrCol *strs, int64_t *d_out_ts,
+                         int64_t *h_out_offsets, int64_t *out_rows) {
+    auto bad = [](const char *msg) {
+        return fail(GS_ERR, (std::string("gs_filter_group: ") + msg).c_str());
+    };
+    if (!ctx || !set || !d_ts || !spec || !d_out_ts || !h_out_offsets ||
+        !out_rows)
+        return bad("NULL argument");
+    FltPlan pl;
+    if (GsStatus st0 = flt_plan("gs_filter_group", true, set, spec, ncols,
+                                cols, nstr, strs, pl))
+        return st0;
+    std::vector<FltCol> &fc = pl.fc;
+    const std::vector<int> &pstr = pl.pstr;
+    const int64_t rows = set->total_rows;
+    const int ng = int(set->ngroups);
+    const int64_t nseg = pl.nseg;
 
     HIP_TRY(hipSetDevice(ctx->device));
     if (rows == 0) {
@@ -5595,14 +6028,6 @@ GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
     int64_t *d_seg_cnt = set->d_flt_seg;
     int64_t *d_seg_off = d_seg_cnt + nseg;        /* [nseg + 1] */
     int64_t *d_seg_bsums = d_seg_off + nseg + 1;  /* [seg_blocks + 1] */
-    if (set->flt_ranges_cap < rtab.size()) {
-        if (set->d_flt_ranges) hipFree(set->d_flt_ranges);
-        set->d_flt_ranges = nullptr;
-        set->flt_ranges_cap = 0;
-        HIP_TRY(hipMalloc(&set->d_flt_ranges,
-                          rtab.size() * sizeof(GsTimeRange)));
-        set->flt_ranges_cap = rtab.size();
-    }
     /* per projected string column a reference array, then the lengths and
        the offset scan's block sums */
     const int64_t row_blocks = (rows + scan_chunk - 1) / scan_chunk;
@@ -5630,23 +6055,8 @@ GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
         ~EvGuard() { hipEventDestroy(e[0]); hipEventDestroy(e[1]); }
     } guard{ev};
 
-    if (!rtab.empty())
-        HIP_TRY(hipMemcpyAsync(set->d_flt_ranges, rtab.data(),
-                               rtab.size() * sizeof(GsTimeRange),
-                               hipMemcpyHostToDevice, ctx->stream));
     FltMaskArgs ma;
-    memset(&ma, 0, sizeof(ma));
-    ma.ts = d_ts;
-    ma.ranges = set->d_flt_ranges;
-    ma.rows = rows;
-    ma.lo = spec->range.min_ts;
-    ma.hi = spec->range.max_ts;
-    ma.row_rng_cnt = row_cnt;
-    ma.npreds = npreds;
-    for (int p = 0; p < npreds; p++) {
-        ma.pred[p] = spec->preds[p];
-        ma.pcol[p] = fc[spec->preds[p].col];
-    }
+    if (GsStatus st0 = flt_mask_args(ctx, set, d_ts, spec, pl, ma)) return st0;
     FltGatherArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.ts = d_ts;
@@ -5738,6 +6148,150 @@ GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
     if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
         g_flt_ms.store(ms, std::memory_order_relaxed);
     return st;
+}
+
+/* ---- typed bucket aggregates over a filtered column group (see
+ * cnosdb_gs.h) ---- */
+
+/* debug: device time of the last gs_agg_group call, first to last kernel,
+   from HIP events on the engine stream */
+static std::atomic<float> g_agg_ms{0.f};
+float gs_debug_agg_ms(void) {
+    return g_agg_ms.load(std::memory_order_relaxed);
+}
+
+GsStatus gs_agg_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
+                      const GsFilterSpec *filter, int32_t ncols,
+                      const GsFilterCol *cols, int32_t nstr,
+                      const GsFilterStrCol *strs, const GsAggSpec *agg,
+                      int32_t naggs, const GsAggOut *outs, int64_t *d_rows) {
+    auto bad = [](const char *msg) {
+        return fail(GS_ERR, (std::string("gs_agg_group: ") + msg).c_str());
+    };
+    if (!ctx || !set || !d_ts || !filter || !agg) return bad("NULL argument");
+    FltPlan pl;
+    if (GsStatus st0 = flt_plan("gs_agg_group", false, set, filter, ncols,
+                                cols, nstr, strs, pl))
+        return st0;
+    if (naggs < 1 || naggs > GS_MAX_MERGE_COLS)
+        return bad("naggs outside 1..GS_MAX_MERGE_COLS");
+    if (!outs) return bad("NULL argument");
+    for (int i = 0; i < naggs; i++)
+        if (outs[i].col < 0 || outs[i].col >= ncols)
+            return bad("aggregated column out of range (fixed-width columns "
+                       "only)");
+    if (agg->n_buckets < 1) return bad("n_buckets < 1");
+    if (agg->bucket_ns < 0) return bad("bucket_ns < 0");
+    if (agg->bucket_ns == 0 && agg->n_buckets != 1)
+        return bad("bucket_ns == 0 takes n_buckets == 1");
+    const int64_t rows = set->total_rows;
+    const int nsg = set->nsgroups;
+    const int64_t scells = int64_t(nsg) * agg->n_buckets;
+    const bool per_series = agg->per_series != 0;
+    const int64_t cells = per_series ? scells : int64_t(agg->n_buckets);
+    if (cells > INT32_MAX) return bad("more than 2^31 - 1 cells");
+    const int ncol = naggs + (d_rows ? 1 : 0);
+    const int64_t nseg = pl.nseg, nrec = 2 * nseg;
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    /* the column table: the aggregated columns, then the row counter */
+    std::vector<AggCol> hc;
+    hc.resize(size_t(ncol));
+    memset(hc.data(), 0, hc.size() * sizeof(AggCol));
+    for (int i = 0; i < naggs; i++) {
+        AggCol &c = hc[i];
+        c.c = pl.fc[outs[i].col];
+        c.o_count = outs[i].d_count;
+        c.o_sum = outs[i].d_sum;
+        c.o_mn = outs[i].d_min;
+        c.o_mx = outs[i].d_max;
+        c.o_first = outs[i].d_first;
+        c.o_last = outs[i].d_last;
+        c.o_first_ts = outs[i].d_first_ts;
+        c.o_last_ts = outs[i].d_last_ts;
+    }
+    if (d_rows) {
+        hc[naggs].c.ctype = GS_CT_TIME; /* val NULL: every kept row counts */
+        hc[naggs].o_count = d_rows;
+    }
+    if (!set->d_agg_cols)
+        HIP_TRY(hipMalloc(&set->d_agg_cols,
+                          (GS_MAX_MERGE_COLS + 1) * sizeof(AggCol)));
+    auto grow = [](uint64_t *&p, size_t &cap, size_t need) {
+        if (cap >= need) return hipSuccess;
+        if (p) hipFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipMalloc(&p, need * 8);
+        if (e == hipSuccess) cap = need;
+        return e;
+    };
+    HIP_TRY(grow(set->d_agg_carry, set->agg_carry_cap,
+                 size_t(nrec) * (1 + size_t(AGG_NFIELD) * ncol)));
+    if (!per_series)
+        HIP_TRY(grow(set->d_agg_scr, set->agg_scr_cap,
+                     size_t(scells) * AGG_NFIELD * ncol));
+
+    hipEvent_t ev[2];
+    HIP_TRY(hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) {
+        hipEventDestroy(ev[0]);
+        return bad("hipEventCreate failed");
+    }
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard() { hipEventDestroy(e[0]); hipEventDestroy(e[1]); }
+    } guard{ev};
+
+    FltMaskArgs ma;
+    if (GsStatus st0 = flt_mask_args(ctx, set, d_ts, filter, pl, ma))
+        return st0;
+    const AggCol *d_cols = (const AggCol *)set->d_agg_cols;
+    HIP_TRY(hipMemcpyAsync(set->d_agg_cols, hc.data(),
+                           hc.size() * sizeof(AggCol), hipMemcpyHostToDevice,
+                           ctx->stream));
+    AggGeom g;
+    memset(&g, 0, sizeof(g));
+    g.sg = set->d_sgroups;
+    g.nsg = nsg;
+    g.nb = agg->n_buckets;
+    g.t0 = agg->t0;
+    g.bn = agg->bucket_ns;
+    g.ncol = ncol;
+    g.scratch = per_series ? nullptr : set->d_agg_scr;
+    g.scells = scells;
+    g.ckey = (int64_t *)set->d_agg_carry;
+    g.ctab = set->d_agg_carry + nrec;
+    g.nrec = nrec;
+
+    HIP_TRY(hipEventRecord(ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_agg_init,
+                       dim3(grid_for(per_series ? cells : scells, 256)),
+                       dim3(256), 0, ctx->stream, g, d_cols, cells);
+    if (nseg > 0) {
+        const int64_t ntile = (nseg + 3) / 4;
+        hipLaunchKernelGGL(k_agg_seg, dim3(grid_items(ntile, 2048)), dim3(256),
+                           0, ctx->stream, ma, g, d_cols, nseg, ctx->d_err);
+        hipLaunchKernelGGL(k_agg_stitch, dim3(grid_for(nrec * ncol * 64, 256)),
+                           dim3(256), 0, ctx->stream, g, d_cols);
+    }
+    if (!per_series)
+        hipLaunchKernelGGL(k_agg_fold,
+                           dim3(grid_for(int64_t(g.nb) * ncol * 64, 256)),
+                           dim3(256), 0, ctx->stream, g, d_cols);
+    HIP_TRY(hipEventRecord(ev[1], ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+        g_agg_ms.store(ms, std::memory_order_relaxed);
+    unsigned e = 0;
+    HIP_TRY(hipMemcpy(&e, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (e) {
+        hipMemset(ctx->d_err, 0, sizeof(unsigned));
+        return fail(GS_ERR_FORMAT, "gs_agg_group: timestamps do not strictly "
+                                   "increase inside a series");
+    }
+    return GS_OK;
 }
 
 /* ---- Arrow C Data Interface export ---- */

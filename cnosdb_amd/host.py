@@ -139,6 +139,19 @@ class GsFilterSpec(ctypes.Structure):
                 ("npreds", ctypes.c_int32)]
 
 
+class GsAggSpec(ctypes.Structure):
+    _fields_ = [("t0", ctypes.c_int64), ("bucket_ns", ctypes.c_int64),
+                ("n_buckets", ctypes.c_int32), ("per_series", ctypes.c_int32)]
+
+
+class GsAggOut(ctypes.Structure):
+    _fields_ = [("col", ctypes.c_int32), ("d_count", ctypes.c_void_p),
+                ("d_sum", ctypes.c_void_p), ("d_min", ctypes.c_void_p),
+                ("d_max", ctypes.c_void_p), ("d_first", ctypes.c_void_p),
+                ("d_last", ctypes.c_void_p), ("d_first_ts", ctypes.c_void_p),
+                ("d_last_ts", ctypes.c_void_p)]
+
+
 # gs_filter_group's ops: gs_scan's seven plus the two null tests
 FILTER_OPS = dict(PRED_OPS, is_null=8, is_not_null=9)
 
@@ -313,6 +326,14 @@ class PageLib:
             ctypes.POINTER(GsFilterCol), ctypes.c_int32,
             ctypes.POINTER(GsFilterStrCol), ctypes.c_void_p, ctypes.c_void_p,
             ctypes.POINTER(ctypes.c_int64)]
+        lib.gs_agg_group.restype = ctypes.c_int32
+        lib.gs_agg_group.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.POINTER(GsFilterSpec), ctypes.c_int32,
+            ctypes.POINTER(GsFilterCol), ctypes.c_int32,
+            ctypes.POINTER(GsFilterStrCol), ctypes.POINTER(GsAggSpec),
+            ctypes.c_int32, ctypes.POINTER(GsAggOut), ctypes.c_void_p]
+        lib.gs_debug_agg_ms.restype = ctypes.c_float
         lib.gs_debug_filter_tile.restype = ctypes.c_int32
         lib.gs_debug_filter_ms.restype = ctypes.c_float
         lib.gs_debug_set_grid_cap.restype = ctypes.c_int32
@@ -778,29 +799,13 @@ class Engine:
             raise e
         return rows.value, offs, totals
 
-    def filter_group(self, gset, d_ts, cols, preds, str_cols=(),
-                     time_range=None, row_tombstones=(), d_out_ts=None):
-        """DataFilter over a column group (gs_filter_group): one mask from
-        the time range, the row tombstones and a conjunction of typed
-        predicates, and every projected column compacted by it.
-
-        cols[c] = (ctype, d_val, d_valid, tombstones, d_out_val,
-        d_out_valid); everything after d_val may be left out or None
-        (d_out_val None = the column only serves predicates).
-        str_cols[s] = ((d_offsets, d_bytes, d_valid), tombstones, out) in
-        decode_str's layout, out = (d_offsets, d_bytes, d_valid) or None.
-        preds = [(col, op, a[, b])], op one of FILTER_OPS ("gt" ... "between",
-        "is_null", "is_not_null"), col >= len(cols) naming a string column;
-        the constants are Python ints, floats or bools, converted to raw
-        bits in the column's own type by pred_bits, which refuses what does
-        not fit.  Tombstones are lists of closed (min_ts, max_ts).
-
-        Returns (out_rows, offsets ndarray of ngroups + 1); the byte totals
-        of the projected string columns are left in self.filter_str_totals
-        (None for a column without output).  The exception of a failed call
-        carries .status (GsStatus), and for GS_ERR_CAP .total_bytes,
-        .out_rows and .offsets: size the byte buffers and call again."""
-        ncols, nstr = len(cols), len(str_cols)
+    @staticmethod
+    def _filter_args(cols, preds, str_cols, time_range, row_tombstones):
+        """cols / preds / str_cols / time_range / row_tombstones of
+        filter_group and agg_group as the C structs.  Returns (fcols, fstrs,
+        spec, souts, keep): souts the GsStrColumnOut of every string column
+        (None without output), keep whatever the structs point into."""
+        ncols = len(cols)
         keep = []
 
         def ptr(t):
@@ -829,7 +834,7 @@ class Engine:
             fcols[c].n_tombstones = tn
             fcols[c].d_out_val = ptr(d_out_val)
             fcols[c].d_out_valid = ptr(d_out_valid)
-        fstrs = (GsFilterStrCol * max(nstr, 1))()
+        fstrs = (GsFilterStrCol * max(len(str_cols), 1))()
         souts = []
         for s, col in enumerate(str_cols):
             col = tuple(col) + (None,) * (3 - len(col))
@@ -848,6 +853,7 @@ class Engine:
             souts.append(o)
             fstrs[s].out = ctypes.pointer(o)
         parr = (GsColPred * max(len(preds), 1))()
+        keep.append(parr)
         for p, pred in enumerate(preds):
             col, op = int(pred[0]), pred[1]
             parr[p].col = col
@@ -869,6 +875,37 @@ class Engine:
         if preds:
             spec.preds = parr
         spec.npreds = len(preds)
+        return fcols, fstrs, spec, souts, keep
+
+    def filter_group(self, gset, d_ts, cols, preds, str_cols=(),
+                     time_range=None, row_tombstones=(), d_out_ts=None):
+        """DataFilter over a column group (gs_filter_group): one mask from
+        the time range, the row tombstones and a conjunction of typed
+        predicates, and every projected column compacted by it.
+
+        cols[c] = (ctype, d_val, d_valid, tombstones, d_out_val,
+        d_out_valid); everything after d_val may be left out or None
+        (d_out_val None = the column only serves predicates).
+        str_cols[s] = ((d_offsets, d_bytes, d_valid), tombstones, out) in
+        decode_str's layout, out = (d_offsets, d_bytes, d_valid) or None.
+        preds = [(col, op, a[, b])], op one of FILTER_OPS ("gt" ... "between",
+        "is_null", "is_not_null"), col >= len(cols) naming a string column;
+        the constants are Python ints, floats or bools, converted to raw
+        bits in the column's own type by pred_bits, which refuses what does
+        not fit.  Tombstones are lists of closed (min_ts, max_ts).
+
+        Returns (out_rows, offsets ndarray of ngroups + 1); the byte totals
+        of the projected string columns are left in self.filter_str_totals
+        (None for a column without output).  The exception of a failed call
+        carries .status (GsStatus), and for GS_ERR_CAP .total_bytes,
+        .out_rows and .offsets: size the byte buffers and call again."""
+        ncols, nstr = len(cols), len(str_cols)
+        fcols, fstrs, spec, souts, _keep = self._filter_args(
+            cols, preds, str_cols, time_range, row_tombstones)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
         offs = np.zeros(gset.ngroups + 1, dtype=np.int64)
         rows = ctypes.c_int64(0)
         st = self.lib.gs_filter_group(
@@ -885,6 +922,55 @@ class Engine:
             e.out_rows, e.offsets = rows.value, offs
             raise e
         return rows.value, offs
+
+    AGG_NAMES = ("count", "sum", "min", "max", "first", "last", "first_ts",
+                 "last_ts")
+
+    def agg_group(self, gset, d_ts, cols, preds, aggs, t0, bucket_ns,
+                  n_buckets, per_series=True, str_cols=(), time_range=None,
+                  row_tombstones=(), d_rows=None):
+        """Typed bucket aggregates over a filtered column group
+        (gs_agg_group): the keep rule of filter_group, and the kept,
+        effectively valid cells of the aggregated columns reduced into
+        (series, bucket) cells without any row output.
+
+        cols / preds / str_cols / time_range / row_tombstones exactly as
+        filter_group takes them (output tensors in cols are ignored).
+        aggs = [(col, {"count": tensor, "sum": tensor, "min": ..., "max":
+        ..., "first": ..., "last": ..., "first_ts": ..., "last_ts": ...})]:
+        col an index into cols, every tensor a CUDA tensor of 8 bytes per
+        cell (gset series * n_buckets cells with per_series, else
+        n_buckets), names left out are not computed.  Values come back as
+        raw bits in the column's type: view the tensor as the column's
+        dtype.  d_rows (int64, one per cell) receives the kept rows per
+        cell.  Every cell of every tensor is written by the call.  The
+        exception of a failed call carries .status (GsStatus)."""
+        ncols, nstr = len(cols), len(str_cols)
+        fcols, fstrs, spec, _souts, _keep = self._filter_args(
+            cols, preds, str_cols, time_range, row_tombstones)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        aspec = GsAggSpec(int(t0), int(bucket_ns), int(n_buckets),
+                          1 if per_series else 0)
+        outs = (GsAggOut * max(len(aggs), 1))()
+        for i, (col, want) in enumerate(aggs):
+            unknown = set(want) - set(self.AGG_NAMES)
+            if unknown:
+                raise ValueError(f"unknown aggregates {sorted(unknown)}")
+            outs[i].col = int(col)
+            for name in self.AGG_NAMES:
+                setattr(outs[i], "d_" + name, ptr(want.get(name)))
+        st = self.lib.gs_agg_group(
+            self._ctx, gset._h, ptr(d_ts), ctypes.byref(spec), ncols,
+            fcols if ncols else None, nstr, fstrs if nstr else None,
+            ctypes.byref(aspec), len(aggs), outs if aggs else None,
+            ptr(d_rows))
+        if st != 0:
+            e = RuntimeError(f"gs_agg_group failed ({st}): {self._pl.err()}")
+            e.status = st
+            raise e
 
     def encode_pages_dev(self, kind, d_vals, row_off, rows, d_out,
                          cap_per_page, d_valid=None):
@@ -1257,6 +1343,12 @@ def filter_ms():
     """Device time of the last filter_group call, first to last kernel,
     from HIP events on the engine stream (gs_debug_filter_ms)."""
     return float(PageLib().lib.gs_debug_filter_ms())
+
+
+def agg_ms():
+    """Device time of the last agg_group call, first to last kernel, from
+    HIP events on the engine stream (gs_debug_agg_ms)."""
+    return float(PageLib().lib.gs_debug_agg_ms())
 
 
 def grid_rounds(reset=False):

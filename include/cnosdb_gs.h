@@ -643,6 +643,105 @@ GsStatus gs_filter_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
                          int64_t *h_out_offsets, /* [gs_set_groups + 1] */
                          int64_t *out_rows);
 
+/* ---- Typed bucket aggregates over a filtered column group ----
+ * gs_agg_group evaluates the keep rule of gs_filter_group and reduces the
+ * kept, effectively valid cells of any fixed-width column straight into
+ * (series, bucket) cells: count, sum, min, max, first and last in the
+ * column's own type.  No row output is written; what gs_filter_group would
+ * have handed to a host-side aggregation (`max(usage_user), min(usage_idle)
+ * WHERE usage_system > 90 AND usage_nice IS NOT NULL GROUP BY time(5m)`,
+ * TSBS lastpoint, any aggregate over an i64 counter) stays on the device.
+ *
+ * Keep rule and validity.  Word for word those of gs_filter_group, on the
+ * same GsFilterSpec / GsFilterCol / GsFilterStrCol and through the same
+ * code.  d_out_val / d_out_valid / out are ignored; string columns serve
+ * predicates only; a raw set (gs_raw_set) works like a page set.
+ *
+ * Series.  A series is a series-level group of the set (gs_set_series:
+ * consecutive column groups of one series_id merged).
+ *
+ * Buckets.  A row with ts < t0 is in no bucket.  Otherwise
+ * b = uint64(ts - t0) / bucket_ns, formed without signed overflow, and
+ * b >= n_buckets is in no bucket.  bucket_ns == 0 is one bucket that holds
+ * every row, whatever t0.  Rows in no bucket contribute to nothing, d_rows
+ * included.
+ *
+ * Cells.  per_series 1: cell s * n_buckets + b of gs_set_series * n_buckets;
+ * per_series 0: cell b of n_buckets, reduced over the series.  Every cell of
+ * every requested array is written by the call exactly as defined: the
+ * caller pre-fills nothing and the call does not accumulate into the
+ * buffers (unlike gs_scan).  An empty cell holds count 0, sum 0 bits, min /
+ * max the starting values of the page statistics (INT64_MAX / INT64_MIN,
+ * UINT64_MAX / 0, bool 1 / 0, f64 +inf / -inf: gs_scan's -inf convention
+ * for max), first / last 0 bits, first_ts INT64_MAX, last_ts INT64_MIN.
+ *
+ * count is the number of kept rows whose cell is effectively valid; d_rows
+ * the number of kept rows (COUNT(*)).  sum is raw bits: f64 for f64, i64 and
+ * u64 wrapping modulo 2^64, for bool the number of true cells as u64.
+ * Whether DataFusion 27's SUM wraps or errors on integer overflow is NOT
+ * VERIFIED here; no parity with the reference is claimed on a sum that
+ * overflows.
+ *
+ * Min and max use strict compares in the column's type, in row order: a
+ * NaN changes neither bound, and of +0.0 and -0.0 the extremum keeps the
+ * bits of the first in row order (the rule of gs_encode_group_pages_dev's
+ * page statistics).  A NaN counts, propagates through sum and can be first
+ * / last.  first / last are the values at the smallest / largest kept
+ * timestamp with a valid cell, first_ts / last_ts those timestamps.
+ *
+ * f64 sum.  The bits are the same for two identical calls and for any
+ * launch grid; apart from that the summation order is the implementation's.
+ * Integer sums are exact modulo 2^64, so order-free.
+ *
+ * per_series 0.  The same aggregates reduced over the series.  first is the
+ * smallest timestamp, among equal timestamps the lowest series index; last
+ * the largest timestamp, among equal timestamps the highest series index:
+ * row order of the concatenated set.  Min / max ties between +0.0 and -0.0
+ * likewise go to the first row of the set.  The (series, bucket) partials
+ * are held in device scratch of gs_set_series * n_buckets cells per
+ * aggregated column for the time of the call.
+ *
+ * Precondition.  Timestamps strictly increase inside a series, as decode
+ * leaves them.  A violation returns GS_ERR_FORMAT (the gs_compact_merge
+ * rule); the output buffers are then unspecified.
+ *
+ * GS_ERR (with a message, before any device work) for everything
+ * gs_filter_group refuses, naggs outside 1..GS_MAX_MERGE_COLS, an
+ * outs[i].col outside 0..ncols-1, n_buckets < 1, bucket_ns < 0,
+ * bucket_ns == 0 with n_buckets != 1, more than 2^31 - 1 cells, or a NULL
+ * required pointer.  A failed call leaves the context usable.  A set with
+ * zero rows succeeds and writes the empty-cell values. */
+typedef struct {
+    int64_t t0;          /* bucket origin */
+    int64_t bucket_ns;   /* >= 1; 0 = one bucket holding every row
+                            (n_buckets must be 1) */
+    int32_t n_buckets;   /* >= 1 */
+    int32_t per_series;  /* 1: cells [gs_set_series * n_buckets], index
+                            s * n_buckets + b
+                            0: cells [n_buckets], reduced over the series */
+} GsAggSpec;
+
+typedef struct {          /* one aggregated column; every array is device
+                             memory of 8 B per cell, NULL = not wanted */
+    int32_t col;          /* index into cols[] (fixed-width columns only) */
+    int64_t *d_count;     /* kept rows whose cell is effectively valid */
+    uint64_t *d_sum;      /* raw bits: f64 -> f64; i64 -> i64 and u64 -> u64,
+                             both wrapping; bool -> u64 number of true cells */
+    uint64_t *d_min, *d_max;     /* raw bits in the column's type, bool 0/1 */
+    uint64_t *d_first, *d_last;  /* value at the smallest / largest kept
+                                    timestamp with a valid cell */
+    int64_t *d_first_ts, *d_last_ts;
+} GsAggOut;
+
+GsStatus gs_agg_group(GsCtx *ctx, GsGroupSet *set, const int64_t *d_ts,
+                      const GsFilterSpec *filter,
+                      int32_t ncols, const GsFilterCol *cols,
+                      int32_t nstr, const GsFilterStrCol *strs,
+                      const GsAggSpec *agg, int32_t naggs,
+                      const GsAggOut *outs,
+                      int64_t *d_rows /* [cells] kept rows per cell
+                                         (COUNT(*)); may be NULL */);
+
 /* ---- Arrow C Data Interface export (decode output as
  * ArrowArray so the Rust shim reconstitutes RecordBatches zero-copy from
  * the shim's side).  GsArrowArray is layout-identical to `struct
